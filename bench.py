@@ -10,7 +10,10 @@ process before anything touches the GPU, and exits with the child's exit code
 world size, next to the backend and the visible device count.
 W untimed warmup steps, then EXACTLY K timed steps bracketed by barrier +
 torch.cuda.synchronize() on both sides; the max elapsed over ranks is used and
-rank 0 prints one JSON line. ``value`` = whole-job tokens/s (all GPUs).
+rank 0 prints one JSON line. ``value`` = whole-job tokens/s (all GPUs), ``ms_per_step`` the
+milliseconds one timed step took. A plain run does only that: set up, warm up, time the K steps.
+``--dump-outputs DIR`` then also writes what the last timed step computed (``dump_outputs``) as
+``DIR/<name>.npy``; ``--full`` is where measurements beyond the headline figure go (none here yet).
 
 A step is a full training step: forward, fused CE loss, backward (per-layer
 RCCL gradient buckets overlapped with backward when N>1), grad-norm clip,
@@ -88,10 +91,50 @@ def main(argv=None):
                          "(env SPA_GRAD_FP32=1)")
     ap.add_argument("--gemm-table", default=None, help="TunableOp GEMM table (default tuning/tunableop_llama8b.csv; "
                     "SPA_GEMM_TUNING=0 disables)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever this file measures beyond the headline figure. It measures nothing else "
+                         "(the other workloads and the parity checks are bench/*.py), so this changes nothing yet")
     a = ap.parse_args(argv)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a.gpus, argv)
     return run(a)
+
+
+DUMP_SAMPLE = 1 << 20   # elements of the flat buffers kept by --dump-outputs (fixed, seeded indices)
+
+
+def dump_outputs(out_dir, flat, opt, losses, sharded):
+    """--dump-outputs: what a caller of the timed step holds after the last one, as float32 /
+    float64 .npy files (about 20 MB): the loss of each of its micro-batches, the global gradient
+    norm, and the same seeded sample of the flat gradient buffer, the flat (model-dtype)
+    parameters and, unless ZeRO-1 shards it, the fp32 master copy after the update. Inputs and
+    initial weights are seeded, so two builds run with the same arguments compare file by file."""
+    import numpy as np
+    import torch
+    flat.wait_all()                      # the overlapped optimizer's last buckets
+    if flat.device.type == "cuda":
+        torch.cuda.synchronize()
+    n = flat.numel
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20240229)).sort().values
+    di = idx.to(flat.device)
+    arrays = {
+        "loss": torch.stack([l.detach().double().reshape(()) for l in losses]).cpu(),
+        "sample_index": idx.double(),
+        "grad_sample": flat.grad[di].float().cpu(),
+        "param_sample": flat.param[di].float().cpu(),
+    }
+    if opt.last_grad_norm is not None:
+        arrays["grad_norm"] = opt.last_grad_norm.detach().double().reshape(1).cpu()
+    if opt.master is not None and not sharded:
+        arrays["master_sample"] = opt.master[di].float().cpu()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
 
 
 def run(a):
@@ -146,9 +189,11 @@ def run(a):
         return t[:, :-1], t[:, 1:]
 
     last_loss = [None]
+    mb_losses = []                       # the last step's micro-batch losses (--dump-outputs)
 
     def step():
         opt.zero_grad()
+        mb_losses.clear()
         for i in range(a.accum):
             x, y = batch()
             sync = (i == a.accum - 1)
@@ -157,6 +202,8 @@ def run(a):
                     loss = model(x, y) / a.accum
                 with annotate("backward"):
                     loss.backward()
+            if a.dump_outputs:
+                mb_losses.append(loss.detach())
         if dp is not None:
             with annotate("grad_sync"):
                 dp.finish_grad_sync()
@@ -178,6 +225,8 @@ def run(a):
     t1 = time.perf_counter()
     elapsed = sdist.all_reduce_max(t1 - t0)
     loss_v = float(last_loss[0].item()) * a.accum
+    if a.dump_outputs and info.is_main:
+        dump_outputs(a.dump_outputs, flat, opt, [l * a.accum for l in mb_losses], bool(a.zero1 and dp is not None))
 
     tokens = world * B * T * a.accum * a.steps
     tok_s = tokens / elapsed

@@ -41,6 +41,30 @@ def test_bench_single_rank_default():
     assert out["n_gpus"] == 1 and out["world_size"] == 1 and out["launcher"] == "direct"
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32 / float64 .npy files, equal
+    from run to run with the same arguments (seeded inputs and weights); --steps sets the number
+    of timed steps (another count gives other parameters), and --full is accepted."""
+    import numpy as np
+    runs = []
+    for name, extra in (("a", ["--steps", "2"]), ("b", ["--steps", "2", "--full"]), ("c", ["--steps", "3"])):
+        d = tmp_path / name
+        r, lines = _run_bench("--dump-outputs", str(d), *extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == int(extra[1]) and out["ms_per_step"] > 0
+        runs.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    a, b, c = runs
+    assert {"loss.npy", "grad_norm.npy", "grad_sample.npy", "param_sample.npy", "sample_index.npy"} <= set(a)
+    assert set(a) == set(b) == set(c)
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+    assert a["loss.npy"].shape == (1,) and a["grad_sample.npy"].shape == a["param_sample.npy"].shape
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert not np.array_equal(a["param_sample.npy"], c["param_sample.npy"])
+
+
 def test_bench_failing_rank_propagates_exit_code():
     # an unknown preset makes every rank raise: the parent must exit non-zero
     r, lines = _run_bench("--gpus", "2", "--model", "no_such_model")
