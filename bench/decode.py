@@ -2,8 +2,9 @@
 """KV-cached generation throughput (serving-side bench): prompt prefill + N decode steps.
 
 Default: LLaMA3-8B shape, bf16, random-init weights, synthetic prompt. Reports prefill
-tok/s and decode tok/s (all sequences); one JSON line. The reference decodes by re-running
-the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
+tok/s and decode tok/s (all sequences); one JSON line. ``--weights fp8`` decodes from the
+block-scaled e4m3 images of infer.quantize_decode_weights (prefill stays on bf16). The
+reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
 from __future__ import annotations
 
 import argparse
@@ -50,8 +51,16 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--graph", action="store_true", help="HIP-graph decode (one replay per token)")
     ap.add_argument("--set", action="append", default=[], help="config override key=value")
+    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: decode products read e4m3 weight images (128x128 E8M0 block scales)")
     a = ap.parse_args(argv)
     m = build(a.model, a.layers, a.set).eval()
+    extra = {}
+    if a.weights == "fp8":
+        from solvingpapers_amd.infer import quantize_decode_weights
+        rep = quantize_decode_weights(m)
+        extra = {"weights": rep["format"], "image_bytes": rep["image_bytes"],
+                 "quantized_params": len(rep["quantized"]), "bf16_params": len(rep["bf16"])}
     ids = torch.randint(0, m.c.vocab_size, (a.batch, a.prompt), device="cuda")
     st = GenerationStats()
     if a.graph:
@@ -68,7 +77,7 @@ def main(argv=None):
                       "decode_tok_s": round(st.decode_tok_s, 2),
                       "ms_per_token": round(1e3 * st.decode_s / max(1, st.new_tokens // a.batch), 3),
                       "dtype": "bf16", "data": "synthetic prompt, random-init weights",
-                      "out_len": out.shape[1]}), flush=True)
+                      "out_len": out.shape[1], **extra}), flush=True)
 
 
 if __name__ == "__main__":

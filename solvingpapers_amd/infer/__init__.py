@@ -4,7 +4,10 @@
 * :class:`KVCache` -- preallocated per-layer K/V buffers, written in place;
 * :func:`generate` -- prompt prefill (flash attention) + token-by-token decode (split-K
   decode kernel, csrc/kernels/decode.hip) with the model's own cache layout, timing
-  prefill and decode separately.
+  prefill and decode separately;
+* :func:`quantize_decode_weights` / :func:`clear_decode_weights` -- fp8 weight-only decode:
+  block-scaled e4m3 images of the projection matrices, read by the decode GEMV kernels
+  (csrc/kernels/gemv_w8.hip); see infer/quant.py.
 
 Reference entry points (all recompute the whole prefix per token, no cache):
 gpt/gpt-jax.ipynb:821-829, llama3/LLaMA-jax.ipynb:499-511, gemma/gemma.ipynb:608-630,
@@ -13,6 +16,8 @@ deepseekv3/deepseekv3.ipynb:1849-1873.
 from .cache import KVCache
 from .generate import GenerationStats, generate
 from .graph import DecodeState, GraphDecoder
+from .quant import clear_decode_weights, quantize_decode_weights
 from .sampling import sample
 
-__all__ = ["KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "generate", "sample"]
+__all__ = ["KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "clear_decode_weights", "generate",
+           "quantize_decode_weights", "sample"]

@@ -298,6 +298,17 @@ def _gemv_ok(x, w, b) -> bool:
             and x.data_ptr() % 16 == 0)
 
 
+def _w8_cpu_ok(x, w, b) -> bool:
+    """:func:`_gemv_ok`'s conditions on the CPU: a decode-shaped inference product there reads a
+    weight's fp8 decode image through the oracle, so a quantised model decodes the same on both."""
+    if x.is_cuda or b is not None or w.dim() != 2 or not x.is_floating_point():
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
+        return False
+    K = x.shape[-1]
+    return 1 <= (x.numel() // K if K else 0) <= GEMV_MAX_ROWS
+
+
 class _LinearFP8Fn(torch.autograd.Function):
     """fp8 Linear for the dense projections of the DeepSeek-V3 recipe (arXiv 2412.19437 sec. 3.3):
     forward and dX are e4m3 GEMMs on hipBLASLt (torch._scaled_mm, row-wise fp32 scales: one per
@@ -384,7 +395,22 @@ def _fp8_ok(x, w) -> bool:
 
 def linear(x, w, b=None, fp8=False):
     """y = x w^T (+ b). ``fp8``: e4m3 forward / dX on hipBLASLt with row-wise scales (dims
-    multiples of 16; else bf16)."""
+    multiples of 16; else bf16). A decode-shaped inference product whose weight carries an fp8
+    decode image (infer.quantize_decode_weights) reads the image (``gemv_w8``,
+    csrc/kernels/gemv_w8.hip; on the CPU the dequantised oracle product)."""
+    if getattr(w, "_spa_w8", None) is not None:
+        if _gemv_ok(x, w, b):
+            from .moe import w8_image
+            wq, s = w8_image(w)
+            x2 = x.reshape(-1, x.shape[-1])
+            if x2.stride(0) % 8:
+                x2 = x2.contiguous()
+            return _ext.ops().gemv_w8(x2, wq, s).view(*x.shape[:-1], w.shape[0])
+        if _w8_cpu_ok(x, w, b):
+            from .moe import w8_image
+            from .reference import gemv_w8
+            wq, s = w8_image(w)
+            return gemv_w8(x.reshape(-1, x.shape[-1]), wq, s).to(x.dtype).view(*x.shape[:-1], w.shape[0])
     if fp8 and _fp8_ok(x, w) and not _gemv_ok(x, w, b):
         return _LinearFP8Fn.apply(x, w, b)
     if _gemv_ok(x, w, b):

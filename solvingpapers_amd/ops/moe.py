@@ -270,7 +270,17 @@ def grouped_linear(xp, W, plan: MoEPlan, fp8: bool = False):
     ``fp8``: forward and dX products in OCP e4m3 on the block-scaled MFMA (per-row scales,
     csrc/kernels/moe_fp8.hip); dW stays bf16. Inference with few rows (decode) streams each
     active expert's weights once (``grouped_gemv``, csrc/kernels/gemv.hip) instead of paying a
-    256-row MFMA tile per expert for one or two tokens."""
+    256-row MFMA tile per expert for one or two tokens. Where ``W`` carries an fp8 decode image
+    (infer.quantize_decode_weights) that product reads the image instead
+    (``grouped_gemv_w8``, csrc/kernels/gemv_w8.hip; on the CPU the dequantised oracle product)."""
+    if not torch.is_grad_enabled() and xp.shape[0] <= GEMV_MAX_ROWS and getattr(W, "_spa_w8", None) is not None:
+        if xp.is_cuda and xp.dtype == torch.bfloat16 and W.dtype == torch.bfloat16:
+            wq, s = w8_image(W)
+            return ops().grouped_gemv_w8(xp.contiguous(), wq, s, plan.offsets)
+        if not xp.is_cuda:
+            from .reference import grouped_gemv_w8
+            wq, s = w8_image(W)
+            return grouped_gemv_w8(xp, wq, s, plan.offsets).to(xp.dtype)
     if (xp.is_cuda and not torch.is_grad_enabled() and xp.shape[0] <= GEMV_MAX_ROWS
             and xp.dtype == torch.bfloat16 and W.dtype == torch.bfloat16):
         return ops().grouped_gemv(xp.contiguous(), W.contiguous(), plan.offsets)
@@ -342,6 +352,36 @@ def _e8m0(amax):
     return torch.where(v > 0, e, torch.zeros_like(e)).clamp(-126, 127).to(torch.int32)
 
 
+def quant_weight_fp8_blk_uncached(W):
+    """The images of :func:`quant_weight_fp8_blk`, built anew and kept in no cache (the decode
+    images of infer/quant.py own theirs): the C++ single-pass quantizer for bf16 HIP tensors,
+    the bit-exact torch formula otherwise."""
+    if W.is_cuda and W.dtype == torch.bfloat16:
+        return tuple(ops().quant_weight_fp8_blk(W.detach().contiguous()))
+    E, N, K = W.shape
+    t = W.detach().float().view(E, N // 128, 128, K // 128, 128)
+    e = _e8m0(t.abs().amax(dim=(2, 4)))                       # [E, NB, KB]
+    q = (t * torch.exp2(-e.float())[:, :, None, :, None]).clamp(-448, 448).to(torch.float8_e4m3fn)
+    q = q.view(E, N, K)
+    return (q, q.transpose(1, 2).contiguous(), (e + 127).to(torch.uint8),
+            (e + 127).to(torch.uint8).transpose(1, 2).contiguous())
+
+
+def w8_image(W):
+    """The fp8 decode image (wq, s) that infer.quantize_decode_weights attached to ``W``, or None.
+    The image is valid while the tensor's ``_version`` and ``data_ptr()`` are the recorded ones;
+    a stale one raises (no silent fall-back to the bf16 weights, and none to outdated fp8 ones)."""
+    im = getattr(W, "_spa_w8", None)
+    if im is None:
+        return None
+    wq, s, version, ptr, name = im
+    if W._version != version or W.data_ptr() != ptr:
+        raise RuntimeError(
+            f"fp8 decode image of parameter '{name}' is stale (the weight was updated or moved after "
+            "quantize_decode_weights): call quantize_decode_weights(model) again, or clear_decode_weights(model)")
+    return wq, s
+
+
 def quant_weight_fp8_blk(W):
     """W [E, N, K] -> (wq [E,N,K], wtq [E,K,N], s [E,N/128,K/128], st [E,K/128,N/128]); cached per
     weight version and optimizer step (never while a HIP graph is being captured)."""
@@ -350,16 +390,7 @@ def quant_weight_fp8_blk(W):
     hit = None if capturing else _WQ_CACHE.get(key)
     if hit is not None:
         return hit
-    if W.is_cuda:
-        out = tuple(ops().quant_weight_fp8_blk(W.detach().contiguous()))
-    else:
-        E, N, K = W.shape
-        t = W.detach().float().view(E, N // 128, 128, K // 128, 128)
-        e = _e8m0(t.abs().amax(dim=(2, 4)))                       # [E, NB, KB]
-        q = (t * torch.exp2(-e.float())[:, :, None, :, None]).clamp(-448, 448).to(torch.float8_e4m3fn)
-        q = q.view(E, N, K)
-        out = (q, q.transpose(1, 2).contiguous(), (e + 127).to(torch.uint8),
-               (e + 127).to(torch.uint8).transpose(1, 2).contiguous())
+    out = quant_weight_fp8_blk_uncached(W)
     if not capturing:
         for k in [k for k in _WQ_CACHE if k[:3] == key[:3]]:
             del _WQ_CACHE[k]

@@ -185,3 +185,30 @@ def sgd_(p, master, g, buf, lr, momentum, wd, coef=None):
     if master is not None:
         master.copy_(pf)
     p.copy_(pf.to(p.dtype))
+
+
+def dequant_w8(wq, s):
+    """fp32 weights of a block-scaled e4m3 image: wq [.., N, K] float8_e4m3fn, s [.., N/128, K/128]
+    uint8 E8M0 (one scale per 128 x 128 block, DeepSeek-V3, arXiv 2412.19437 sec. 3.3) ->
+    q * 2^(s - 127). Every value is exact in bf16."""
+    N, K = wq.shape[-2:]
+    lead = wq.shape[:-2]
+    t = wq.float().view(*lead, N // 128, 128, K // 128, 128)
+    return (t * torch.exp2(s.float() - 127)[..., :, None, :, None]).reshape(*lead, N, K)
+
+
+def gemv_w8(x, wq, s):
+    """x [M, K] times the dequantised image [N, K]^T, fp32 (csrc/kernels/gemv_w8.hip)."""
+    return x.float() @ dequant_w8(wq, s).t()
+
+
+def grouped_gemv_w8(x, wq, s, offsets):
+    """Expert-sorted rows x [A, K] times the dequantised image of their expert, wq [E, N, K],
+    offsets [E+1]: fp32 [A, N]."""
+    off = offsets.tolist()
+    w = dequant_w8(wq, s)
+    out = torch.zeros(x.shape[0], wq.shape[1], dtype=torch.float32, device=x.device)
+    for e in range(len(off) - 1):
+        if off[e + 1] > off[e]:
+            out[off[e]:off[e + 1]] = x[off[e]:off[e + 1]].float() @ w[e].t()
+    return out

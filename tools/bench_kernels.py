@@ -2,6 +2,9 @@
 as achieved HBM bandwidth (ideal bytes / time). Run under ``rocprofv3 --pmc`` for counters.
 
 usage: python tools/bench_kernels.py [--iters N] [--only name,name]
+
+``--only gemv`` runs just the decode GEMV rows: the fp8 weight-only kernel (gemv_w8) against the bf16
+kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4.
 """
 import argparse
 import json
@@ -89,6 +92,53 @@ def cases():
     return out
 
 
+GEMV_SHAPES = [(6144, 4096), (4096, 4096), (28672, 4096), (4096, 14336)]   # LLaMA3-8B qkv, o, gate|up, down
+
+
+def _graphed(fn):
+    """``fn``'s launches as one HIP-graph replay (as GraphDecoder issues them): a few-microsecond
+    kernel is timed on the device, not by how fast the host can enqueue it."""
+    fn()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        keep = fn()
+    return lambda g=graph, _outputs=keep: g.replay()
+
+
+def gemv_rows(iters, rounds=3):
+    """gemv_w8 next to gemv, same process, arms alternated A B B A per round. Every call reads another
+    copy of the weight out of a ring larger than the 256 MB last-level cache (both arms: 32 copies at
+    least), as a decode step does, where each matrix is read once per token; one pass over the ring is one
+    HIP-graph replay. Reported: GB/s of WEIGHT bytes and the fp8 / bf16 time ratio (< 1: the fp8 kernel
+    is faster)."""
+    from solvingpapers_amd.ops.moe import quant_weight_fp8_blk_uncached
+    ops = _ext.ops()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for N, K in GEMV_SHAPES:
+        ring = max(32, -(-(1 << 30) // (N * K)))             # >= 1 GB of fp8 bytes, 2 GB of bf16
+        w = torch.randn(N, K, device=DEV, dtype=BF, generator=g)
+        wq, _, s, _ = quant_weight_fp8_blk_uncached(w[None])
+        wb = [w.clone() for _ in range(ring)]
+        wf = [(wq[0].clone(), s[0].clone()) for _ in range(ring)]
+        for M in (1, 4):
+            x = torch.randn(M, K, device=DEV, dtype=BF, generator=g)
+            arms = {"bf16": _graphed(lambda: [ops.gemv(x, wi) for wi in wb]),
+                    "fp8": _graphed(lambda: [ops.gemv_w8(x, q, si) for q, si in wf])}
+            ms = {"bf16": [], "fp8": []}
+            for _ in range(rounds):
+                for arm in ("bf16", "fp8", "fp8", "bf16"):
+                    ms[arm].append(timed(arms[arm], iters) / ring)
+            mb, mf = (sorted(ms[a])[len(ms[a]) // 2] for a in ("bf16", "fp8"))
+            for arm, m_, nbytes in (("gemv", mb, N * K * 2), ("gemv_w8", mf, N * K + N * K // 16384)):
+                print(json.dumps({"kernel": f"{arm}_M{M}_{N}x{K}", "ms": round(m_, 5), "GB": round(nbytes / 1e9, 4),
+                                  "weight_GB_per_s": round(nbytes / m_ / 1e6, 1),
+                                  "min_ms": round(min(ms["bf16" if arm == "gemv" else "fp8"]), 5),
+                                  "max_ms": round(max(ms["bf16" if arm == "gemv" else "fp8"]), 5),
+                                  **({"time_vs_bf16": round(mf / mb, 3)} if arm == "gemv_w8" else {})}), flush=True)
+        del wb, wf
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -96,7 +146,9 @@ def main():
     a = ap.parse_args()
     assert _ext.load(), "HIP extension missing"
     only = set(filter(None, a.only.split(",")))
-    for name, (fn, nbytes) in cases().items():
+    if not only or "gemv" in only:
+        gemv_rows(a.iters)
+    for name, (fn, nbytes) in ({} if only == {"gemv"} else cases()).items():
         if only and name not in only:
             continue
         ms = timed(fn, a.iters)
