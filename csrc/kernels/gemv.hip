@@ -1,13 +1,17 @@
-// Weight-streaming GEMV for decode: y[M, N] = x[M, K] @ W[N, K]^T, bf16 in / out, fp32
-// accumulation, M <= 4 (the decode batch).
+// Weight-streaming GEMV for decode: y[M, N] = x[M, K] @ W[N, K]^T, x / y bf16, fp32 accumulation,
+// M <= 4 (the decode batch), dense and grouped (MoE), for two weight formats:
+//   bf16   W as stored (gemv, grouped_gemv);
+//   e4m3   the fp8 weight-only image: Wq OCP e4m3 [N, K], S uint8 E8M0 [N/128, K/128] (DeepSeek-V3's
+//          128 x 128 block scales, as quant_weight_fp8_blk writes them), w = q * 2^(S - 127); half the
+//          bytes (gemv_w8, grouped_gemv_w8). N % 128 == 0 and K % 128 == 0.
 //
 // A decode step multiplies a handful of token rows by every projection matrix: pure weight
 // streaming (LLaMA3-8B: 16 GB per token), so the kernel is built for HBM, not for MFMA:
-//  * each wave owns RW consecutive rows of W; its lanes split K in 16-byte chunks (lane l
-//    reads k = 8l + 512i), so one wave-instruction reads 1 KB contiguous of a row;
+//  * each wave owns RW consecutive rows of W; its lanes split K in 16-byte chunks (lane l reads
+//    chunk l + 64 i), so one wave-instruction reads 1 KB contiguous of a row;
 //  * U chunks x RW rows of weight loads are issued before any is consumed (U * RW * 16 B in
-//    flight per lane), non-temporal (read once, kept out of L2): latency is hidden by
-//    memory-level parallelism, no LDS round trip (cdna_hip_programming.md, 'GEMV / M <= 16');
+//    flight per lane), non-temporal in the dense kernel (read once, kept out of L2): latency is
+//    hidden by memory-level parallelism, no LDS round trip (cdna_hip_programming.md, 'GEMV / M <= 16');
 //  * RW = 2 for narrow outputs (N < 8192: o-proj, down-proj) so the grid still holds >= 2
 //    waves per SIMD; RW = 4 otherwise;
 //  * x (M x K, a few KB) is re-read per chunk from L1/L2, where it stays;
@@ -15,9 +19,71 @@
 //    reduction per output at the end.
 // torch.mm at M = 1 goes to hipBLASLt 16x16 macro tiles at 2.5-5 TB/s on streamed weights
 // (decode profile: wo 2.5, wqkv 3.3, w13 3.9, w2 5.0 TB/s); this is the op the decode path uses.
+//
+// The loop structure exists once (accumulate_rows); a weight format is a policy struct that says
+// what a 16-byte load holds, how it becomes bf16x8 operands of the dot, and in which of two
+// statement orders the dense kernel consumes a chunk. For e4m3:
+//  * a 16-byte load is 16 weights, so eight consecutive lanes share one K block's scale, and RW
+//    (2 or 4) divides 128, so a wave's rows sit in ONE 128-row block: one scale byte per lane per
+//    1 KB pass, whatever RW is;
+//  * v_cvt_scalef32_pk_bf16_fp8 turns two e4m3 bytes times a float scale into a bf16 pair; with
+//    2^(S - 127) as that scale the block scale is free, and e4m3 times a power of two is exact in
+//    bf16, so the products feed v_dot2_f32_bf16 exactly as bf16 weights do. The conversion is done
+//    once per weight row and reused by all token rows;
+//  * the block exponents are 1..254 (quant_weight_fp8_blk clamps to +-126), so S << 23 is the
+//    scale's fp32 bit pattern.
 #include "spa_common.h"
 
 namespace spa {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// Weight formats. elem: storage type; raw: one 16-byte load = H * 8 weights; BLOCKED: whole 128 x 128
+// blocks, contiguous (no row tail to clamp, row stride K); scale_row: the block scales of weight row
+// `row` of the expert whose scale rows start at `base`; scale: the scale byte of the chunk at
+// k + ahead (ahead: a compile-time multiple of 128, kept apart so that the look-ahead loads share
+// one address register); prepare: raw chunk -> H bf16x8 in K order.
+// ROW_AT_A_TIME<M, RW>: the dense kernel's statement order for a chunk (accumulate_rows). The
+// arithmetic is the same either way; hipcc's load schedule is not, and it decides 1-5 % of the time
+// of these kernels (profiles/gemv_unify.txt). e4m3 converts one weight row at a time (8 VGPRs of
+// converted operands live, not 8 RW); bf16 has nothing to convert and takes that order only at
+// M = RW = 4, where the other one measured 1 % slower. After a toolchain update, rerun
+// tools/kres.sh csrc/kernels/gemv.hip and the timing of that profile: neither is pinned by a test.
+struct WBf16 {
+  using elem = bf16;
+  using raw = bf16x8;
+  static constexpr int H = 1;
+  static constexpr bool BLOCKED = false;
+  template <int M, int RW> static constexpr bool ROW_AT_A_TIME = M * RW == 16;
+  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t*, long, int, int) { return nullptr; }
+  static __device__ __forceinline__ uint8_t scale(const uint8_t*, int, int) { return 0; }
+  static __device__ __forceinline__ void prepare(const raw& q, uint8_t, bf16x8 (&w)[H]) { w[0] = q; }
+};
+
+struct WE4m3 {
+  using elem = uint8_t;
+  using raw = u32x4;
+  static constexpr int H = 2;
+  static constexpr bool BLOCKED = true;
+  template <int M, int RW> static constexpr bool ROW_AT_A_TIME = true;
+  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t* s, long base, int row, int K) {
+    return s + (base + (row >> 7)) * (K >> 7);
+  }
+  static __device__ __forceinline__ uint8_t scale(const uint8_t* sr, int k, int ahead) {
+    return sr[(k >> 7) + (ahead >> 7)];
+  }
+  // dword j holds k = 4j .. 4j + 3, low half first
+  static __device__ __forceinline__ void prepare(const raw& q, uint8_t sb, bf16x8 (&w)[H]) {
+    const float sc = __builtin_bit_cast(float, (unsigned)sb << 23);
+    bf16x4 p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      p[j] = __builtin_shufflevector(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[j], sc, false),
+                                     __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[j], sc, true), 0, 1, 2, 3);
+    w[0] = __builtin_shufflevector(p[0], p[1], 0, 1, 2, 3, 4, 5, 6, 7);
+    w[1] = __builtin_shufflevector(p[2], p[3], 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+};
 
 __device__ __forceinline__ float dot8(const bf16x8& a, const bf16x8& b, float c) {
 #pragma unroll
@@ -29,180 +95,240 @@ __device__ __forceinline__ float dot8(const bf16x8& a, const bf16x8& b, float c)
   return c;
 }
 
-__device__ __forceinline__ bf16x8 ld_stream(const bf16* p) {
-  return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p));
+// acc[m][r] += this lane's share of x[m0 + m, :] . wr[r][:] for the first mn <= MB of those rows of x
+// (row stride ldx): k ascending, every dot2 chain in element order. NT: non-temporal weight loads.
+// ROWWISE (all MB rows live): the x rows of a chunk are loaded first, then each weight row is
+// converted and used; else all weight rows are converted, then each live x row is loaded and used.
+template <class F, int MB, int RW, int U, bool NT, bool ROWWISE>
+__device__ __forceinline__ void accumulate_rows(float (&acc)[MB][RW], const bf16* __restrict__ x, const int m0,
+                                                const long ldx, const int mn,
+                                                const typename F::elem* const (&wr)[RW],
+                                                const uint8_t* __restrict__ sr, const int K, const int lane) {
+  static_assert(128 % RW == 0, "a wave's rows must share one 128-row scale block");
+  using raw = typename F::raw;
+  constexpr int CH = 8 * F::H, PASS = 64 * CH;  // weights per lane / per wave and pass
+  auto load = [](const typename F::elem* p) {
+    return NT ? __builtin_nontemporal_load(reinterpret_cast<const raw*>(p)) : *reinterpret_cast<const raw*>(p);
+  };
+  auto consume = [&](const int k, const raw* wv, const uint8_t sc) {
+    bf16x8 xv[MB][F::H], wp[RW][F::H];
+    auto load_x = [&](const int m) {
+#pragma unroll
+      for (int h = 0; h < F::H; ++h)
+        xv[m][h] = *reinterpret_cast<const bf16x8*>(x + (long)(m0 + m) * ldx + k + 8 * h);
+    };
+    if (ROWWISE) {
+#pragma unroll
+      for (int m = 0; m < MB; ++m) load_x(m);
+#pragma unroll
+      for (int r = 0; r < RW; ++r) {
+        F::prepare(wv[r], sc, wp[r]);
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+#pragma unroll
+          for (int h = 0; h < F::H; ++h) acc[m][r] = dot8(xv[m][h], wp[r][h], acc[m][r]);
+      }
+      return;
+    }
+#pragma unroll
+    for (int r = 0; r < RW; ++r) F::prepare(wv[r], sc, wp[r]);
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      if (m < mn) {
+        load_x(m);
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+          for (int h = 0; h < F::H; ++h) acc[m][r] = dot8(xv[m][h], wp[r][h], acc[m][r]);
+      }
+    }
+  };
+  int k = CH * lane;
+  for (; k + (U - 1) * PASS < K; k += U * PASS) {
+    raw wv[U][RW];
+    uint8_t sc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int r = 0; r < RW; ++r) wv[u][r] = load(wr[r] + k + u * PASS);
+      sc[u] = F::scale(sr, k, u * PASS);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) consume(k + u * PASS, wv[u], sc[u]);
+  }
+  for (; k < K; k += PASS) {
+    raw wv[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) wv[r] = load(wr[r] + k);
+    consume(k, wv, F::scale(sr, k, 0));
+  }
 }
 
-template <int M, int RW, int U>
-__global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                   bf16* __restrict__ y, int N, int K, long ldx, long ldw,
-                                                   long ldy) {
+// Dense: x [M, K] (row stride ldx), w [N, K] (row stride ldw), s: w's block scales -> y [M, N].
+template <class F, int M, int RW, int U>
+__global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ x, const typename F::elem* __restrict__ w,
+                                                   const uint8_t* __restrict__ s, bf16* __restrict__ y, int N, int K,
+                                                   long ldx, long ldw) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   const int row0 = wave * RW;
   if (row0 >= N) return;  // wave-uniform
-  float acc[M][RW];
+  const typename F::elem* wr[RW];
 #pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int r = 0; r < RW; ++r) acc[m][r] = 0.f;
-  const bf16* wr[RW];
-#pragma unroll
-  for (int r = 0; r < RW; ++r) wr[r] = w + (long)min(row0 + r, N - 1) * ldw;  // tail rows: duplicate, not stored
-  auto consume = [&](const int k, const bf16x8* wv) {
-    bf16x8 xv[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) xv[m] = *reinterpret_cast<const bf16x8*>(x + m * ldx + k);
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-#pragma unroll
-      for (int r = 0; r < RW; ++r) acc[m][r] = dot8(xv[m], wv[r], acc[m][r]);
-  };
-  int k = 8 * lane;
-  for (; k + (U - 1) * 512 < K; k += U * 512) {
-    bf16x8 wv[U][RW];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int r = 0; r < RW; ++r) wv[u][r] = ld_stream(wr[r] + k + u * 512);
-#pragma unroll
-    for (int u = 0; u < U; ++u) consume(k + u * 512, wv[u]);
-  }
-  for (; k < K; k += 512) {
-    bf16x8 wv[RW];
-#pragma unroll
-    for (int r = 0; r < RW; ++r) wv[r] = ld_stream(wr[r] + k);
-    consume(k, wv);
-  }
+  for (int r = 0; r < RW; ++r)  // tail rows: duplicate, not stored
+    wr[r] = w + (long)(F::BLOCKED ? row0 + r : min(row0 + r, N - 1)) * (F::BLOCKED ? (long)K : ldw);
+  float acc[M][RW] = {};
+  const uint8_t* sr = F::scale_row(s, 0, row0, K);
+  accumulate_rows<F, M, RW, U, true, F::template ROW_AT_A_TIME<M, RW>>(acc, x, 0, ldx, M, wr, sr, K, lane);
 #pragma unroll
   for (int m = 0; m < M; ++m)
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
       const float v = wave_sum(acc[m][r]);
-      if (lane == m * RW + r && row0 + r < N) y[m * ldy + row0 + r] = (bf16)v;
+      if (lane == m * RW + r && (F::BLOCKED || row0 + r < N)) y[(long)m * N + row0 + r] = (bf16)v;
     }
 }
 
-template <int M>
-static void launch_gemv(const bf16* x, const bf16* w, bf16* y, int N, int K, long ldx, long ldw, hipStream_t st) {
-  if (N >= 8192) gemv_kernel<M, 4, 4><<<cdiv(cdiv(N, 4), 4), 256, 0, st>>>(x, w, y, N, K, ldx, ldw, N);
-  else gemv_kernel<M, 2, 4><<<cdiv(cdiv(N, 2), 4), 256, 0, st>>>(x, w, y, N, K, ldx, ldw, N);
-}
-
-// x [M, K] (row stride ldx), w [N, K] row-major -> y [M, N]; M <= 4, K % 8 == 0.
-at::Tensor gemv(const at::Tensor& x, const at::Tensor& w) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
-              "gemv: bf16 HIP tensors");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "gemv: x [M, K], w [N, K]");
-  const int M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 4, "gemv: M must be 1..4");
-  TORCH_CHECK(K % 8 == 0 && x.stride(1) == 1 && w.stride(1) == 1 && x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 &&
-                  ((uintptr_t)x.data_ptr() % 16) == 0 && ((uintptr_t)w.data_ptr() % 16) == 0,
-              "gemv: rows must be 16-byte aligned with K % 8 == 0");
-  DeviceGuard g(x.device());
-  auto y = at::empty({M, N}, x.options());
-  if (N == 0) return y;
-  auto st = stream();
-  const bf16* xp = (const bf16*)x.data_ptr();
-  const bf16* wp = (const bf16*)w.data_ptr();
-  bf16* yp = (bf16*)y.data_ptr();
-  switch (M) {
-    case 1: launch_gemv<1>(xp, wp, yp, N, K, x.stride(0), w.stride(0), st); break;
-    case 2: launch_gemv<2>(xp, wp, yp, N, K, x.stride(0), w.stride(0), st); break;
-    case 3: launch_gemv<3>(xp, wp, yp, N, K, x.stride(0), w.stride(0), st); break;
-    default: launch_gemv<4>(xp, wp, yp, N, K, x.stride(0), w.stride(0), st); break;
-  }
-  SPA_LAUNCH_CHECK();
-  return y;
-}
-
-
-// ---------------------------------------------------------------------------------------
-// Grouped (MoE) weight-streaming GEMV for decode: y[a, :] = x[a, :] @ W_e^T for the rows
-// a in [off[e], off[e+1]) of every expert e (the expert-sorted assignments of a few tokens:
-// 6 rows over 64 experts at batch 1). The MFMA grouped GEMM pays a 256-row tile per active
-// expert for one or two real rows; this streams each ACTIVE expert's weights once instead.
-// Grid: experts x column chunks; a wave owns RW weight rows (output columns) and walks the
-// expert's token rows in groups of 4 (re-reading its weight rows from L2 past 4 rows).
-// Experts with no rows exit at once (the row counts live on the device: no host sync).
-template <int RW, int U>
-__global__ __launch_bounds__(256) void grouped_gemv_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                           bf16* __restrict__ y, const int* __restrict__ offsets,
-                                                           int N, int K, long strideW) {
+// Grouped (MoE): y[a, :] = x[a, :] @ W_e^T for the rows a in [off[e], off[e+1]) of every expert e
+// (the expert-sorted assignments of a few tokens: 6 rows over 64 experts at batch 1). The MFMA
+// grouped GEMM pays a 256-row tile per active expert for one or two real rows; this streams each
+// ACTIVE expert's weights once instead. Grid: experts x column chunks; a wave owns RW weight rows
+// (output columns) and walks the expert's token rows in groups of 4 (re-reading its weight rows
+// from L2 past 4 rows, hence plain loads). Experts with no rows exit at once (the row counts live
+// on the device: no host sync). x [A, K], w [E, N, K], s [E, N/128, K/128], all contiguous.
+template <class F, int RW, int U>
+__global__ __launch_bounds__(256) void grouped_gemv_kernel(const bf16* __restrict__ x,
+                                                           const typename F::elem* __restrict__ w,
+                                                           const uint8_t* __restrict__ s, bf16* __restrict__ y,
+                                                           const int* __restrict__ offsets, int N, int K) {
   constexpr int MB = 4;
   const int lane = threadIdx.x & 63;
-  const int nwb = cdiv(cdiv(N, RW), 4);  // blocks per expert
+  const int nwb = (N + 4 * RW - 1) / (4 * RW);  // blocks per expert; 32-bit: most blocks only get to the exit below
   const int e = blockIdx.x / nwb;
   const int wave = __builtin_amdgcn_readfirstlane((blockIdx.x % nwb) * 4 + (threadIdx.x >> 6));
   const int r_begin = offsets[e], r_end = offsets[e + 1];
   const int row0 = wave * RW;
   if (r_begin >= r_end || row0 >= N) return;  // wave-uniform
-  const bf16* we = w + (long)e * strideW;
-  const bf16* wr[RW];
+  const typename F::elem* wr[RW];
 #pragma unroll
-  for (int r = 0; r < RW; ++r) wr[r] = we + (long)min(row0 + r, N - 1) * K;
+  for (int r = 0; r < RW; ++r)
+    wr[r] = w + ((long)e * N + (F::BLOCKED ? row0 + r : min(row0 + r, N - 1))) * K;
+  const uint8_t* sr = F::scale_row(s, (long)e * (N >> 7), row0, K);
   for (int m0 = r_begin; m0 < r_end; m0 += MB) {
     const int mn = min(MB, r_end - m0);
-    float acc[MB][RW];
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int r = 0; r < RW; ++r) acc[m][r] = 0.f;
-    auto consume = [&](const int k, const bf16x8* wv) {
-#pragma unroll
-      for (int m = 0; m < MB; ++m) {
-        if (m < mn) {
-          const bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + (long)(m0 + m) * K + k);
-#pragma unroll
-          for (int r = 0; r < RW; ++r) acc[m][r] = dot8(xv, wv[r], acc[m][r]);
-        }
-      }
-    };
-    int k = 8 * lane;
-    for (; k + (U - 1) * 512 < K; k += U * 512) {
-      bf16x8 wv[U][RW];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int r = 0; r < RW; ++r) wv[u][r] = *reinterpret_cast<const bf16x8*>(wr[r] + k + u * 512);
-#pragma unroll
-      for (int u = 0; u < U; ++u) consume(k + u * 512, wv[u]);
-    }
-    for (; k < K; k += 512) {
-      bf16x8 wv[RW];
-#pragma unroll
-      for (int r = 0; r < RW; ++r) wv[r] = *reinterpret_cast<const bf16x8*>(wr[r] + k);
-      consume(k, wv);
-    }
+    float acc[MB][RW] = {};
+    accumulate_rows<F, MB, RW, U, false, false>(acc, x, m0, K, mn, wr, sr, K, lane);
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
         const float v = wave_sum(acc[m][r]);
-        if (lane == m * RW + r && m < mn && row0 + r < N) y[(long)(m0 + m) * N + row0 + r] = (bf16)v;
+        if (lane == m * RW + r && m < mn && (F::BLOCKED || row0 + r < N))
+          y[(long)(m0 + m) * N + row0 + r] = (bf16)v;
       }
   }
 }
 
-// x [A, K] expert-sorted rows, w [E, N, K], offsets [E+1] (device) -> y [A, N]
-at::Tensor grouped_gemv(const at::Tensor& x, const at::Tensor& w, const at::Tensor& offsets) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
-              "grouped_gemv: bf16 HIP tensors");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 3 && x.size(1) == w.size(2) && x.is_contiguous() && w.is_contiguous(),
-              "grouped_gemv: x [A, K], w [E, N, K] contiguous");
-  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.numel() == w.size(0) + 1, "grouped_gemv: offsets [E+1]");
-  const int A = x.size(0), K = x.size(1), E = w.size(0), N = w.size(1);
-  TORCH_CHECK(K % 8 == 0 && ((uintptr_t)x.data_ptr() % 16) == 0 && ((uintptr_t)w.data_ptr() % 16) == 0,
-              "grouped_gemv: K % 8 == 0, 16-byte aligned");
+// Host-side argument checks, shared by the four ops. `lead`: 0 dense, 1 grouped (a leading expert dim).
+// The weight operand: bf16 w [.., N, K], or with `s` its e4m3 image wq [.., N, K] + s [.., N/128, K/128].
+static void check_weight(const char* op, const at::Tensor& w, const at::Tensor* s, int64_t lead) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == lead + 2, op, ": w must be a ", lead + 2, "-D HIP tensor");
+  const int64_t N = w.size(lead), K = w.size(lead + 1);
+  TORCH_CHECK(N < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && ((uintptr_t)w.data_ptr() % 16) == 0, op,
+              ": w must be 16-byte aligned");
+  if (!s) {
+    TORCH_CHECK(w.scalar_type() == at::kBFloat16, op, ": bf16 HIP tensors");
+    // a dense weight may be a row-strided view (a slice of a wider buffer)
+    TORCH_CHECK(K % 8 == 0 && (lead ? w.is_contiguous() : w.stride(1) == 1 && w.stride(0) % 8 == 0), op,
+                ": rows must be 16-byte aligned with K % 8 == 0", lead ? ", w contiguous" : "");
+    return;
+  }
+  TORCH_CHECK(s->is_cuda() && s->device() == w.device() && w.scalar_type() == at::kFloat8_e4m3fn &&
+                  s->scalar_type() == at::kByte,
+              op, ": wq float8_e4m3fn, s uint8 (E8M0) HIP tensors on one device");
+  TORCH_CHECK(w.is_contiguous() && s->is_contiguous(), op, ": wq, s contiguous");
+  TORCH_CHECK(N % 128 == 0 && K % 128 == 0, op, ": N % 128 == 0 and K % 128 == 0 (got N = ", N, ", K = ", K, ")");
+  TORCH_CHECK(s->dim() == lead + 2 && s->size(lead) == N / 128 && s->size(lead + 1) == K / 128 &&
+                  (lead == 0 || s->size(0) == w.size(0)),
+              op, ": s must be [", (lead ? "E, " : ""), "N/128, K/128]");
+}
+
+// x: bf16 [rows, K] on w's device, rows 16-byte aligned (K % 8 == 0 is the weight's check); grouped: contiguous
+static void check_x(const char* op, const at::Tensor& x, const at::Tensor& w, int64_t lead) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.device() == w.device(), op,
+              ": x must be a bf16 HIP tensor on w's device");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == w.size(lead + 1), op, ": x [rows, K], w [.., N, K]");
+  TORCH_CHECK((lead ? x.is_contiguous() : x.stride(1) == 1 && x.stride(0) % 8 == 0) &&
+                  ((uintptr_t)x.data_ptr() % 16) == 0,
+              op, ": x rows must be 16-byte aligned", lead ? ", x contiguous" : "");
+}
+
+template <class F, int M>
+static void launch_gemv(const at::Tensor& x, const at::Tensor& w, const at::Tensor* s, at::Tensor& y) {
+  const int N = w.size(0), K = w.size(1);
+  const auto xp = (const bf16*)x.data_ptr();
+  const auto wp = (const typename F::elem*)w.data_ptr();
+  const auto sp = s ? (const uint8_t*)s->data_ptr() : nullptr;
+  const auto yp = (bf16*)y.data_ptr();
+  if (N >= 8192)
+    gemv_kernel<F, M, 4, 4><<<cdiv(cdiv(N, 4), 4), 256, 0, stream()>>>(xp, wp, sp, yp, N, K, x.stride(0), w.stride(0));
+  else
+    gemv_kernel<F, M, 2, 4><<<cdiv(cdiv(N, 2), 4), 256, 0, stream()>>>(xp, wp, sp, yp, N, K, x.stride(0), w.stride(0));
+}
+
+// x [M, K] bf16 (row stride ldx), w [N, K] (+ s [N/128, K/128]) -> y [M, N] bf16; M <= 4
+template <class F>
+static at::Tensor gemv_op(const char* op, const at::Tensor& x, const at::Tensor& w, const at::Tensor* s) {
+  check_weight(op, w, s, 0);
+  check_x(op, x, w, 0);
+  const int M = x.size(0), N = w.size(0), K = w.size(1);
+  TORCH_CHECK(M >= 1 && M <= 4, op, ": M must be 1..4");
   DeviceGuard g(x.device());
-  auto y = at::empty({A, N}, x.options());
-  if (A == 0 || N == 0) return y;
-  const int nwb = cdiv(cdiv(N, 2), 4);
-  grouped_gemv_kernel<2, 4><<<E * nwb, 256, 0, stream()>>>((const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(),
-                                                          (bf16*)y.data_ptr(), offsets.data_ptr<int>(), N, K,
-                                                          (long)N * K);
+  auto y = at::empty({M, N}, x.options());
+  if (N == 0 || K == 0) return K == 0 ? y.zero_() : y;
+  switch (M) {
+    case 1: launch_gemv<F, 1>(x, w, s, y); break;
+    case 2: launch_gemv<F, 2>(x, w, s, y); break;
+    case 3: launch_gemv<F, 3>(x, w, s, y); break;
+    default: launch_gemv<F, 4>(x, w, s, y); break;
+  }
   SPA_LAUNCH_CHECK();
   return y;
+}
+
+// x [A, K] expert-sorted rows, w [E, N, K] (+ s [E, N/128, K/128]), offsets [E+1] (device) -> y [A, N]
+template <class F>
+static at::Tensor grouped_gemv_op(const char* op, const at::Tensor& x, const at::Tensor& w, const at::Tensor* s,
+                                  const at::Tensor& offsets) {
+  check_weight(op, w, s, 1);
+  check_x(op, x, w, 1);
+  TORCH_CHECK(offsets.is_cuda() && offsets.device() == x.device() && offsets.scalar_type() == at::kInt &&
+                  offsets.is_contiguous() && offsets.numel() == w.size(0) + 1,
+              op, ": offsets int32 [E+1] on the device");
+  const int A = x.size(0), K = x.size(1), E = w.size(0), N = w.size(1);
+  DeviceGuard g(x.device());
+  auto y = at::empty({A, N}, x.options());
+  if (A == 0 || N == 0 || E == 0) return y;
+  if (K == 0) return y.zero_();
+  const int nwb = cdiv(cdiv(N, 2), 4);
+  TORCH_CHECK((int64_t)E * nwb < (int64_t)1 << 31, op, ": grid too large");
+  grouped_gemv_kernel<F, 2, 4><<<E * nwb, 256, 0, stream()>>>(
+      (const bf16*)x.data_ptr(), (const typename F::elem*)w.data_ptr(), s ? (const uint8_t*)s->data_ptr() : nullptr,
+      (bf16*)y.data_ptr(), offsets.data_ptr<int>(), N, K);
+  SPA_LAUNCH_CHECK();
+  return y;
+}
+
+at::Tensor gemv(const at::Tensor& x, const at::Tensor& w) { return gemv_op<WBf16>("gemv", x, w, nullptr); }
+at::Tensor gemv_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& s) {
+  return gemv_op<WE4m3>("gemv_w8", x, wq, &s);
+}
+at::Tensor grouped_gemv(const at::Tensor& x, const at::Tensor& w, const at::Tensor& offsets) {
+  return grouped_gemv_op<WBf16>("grouped_gemv", x, w, nullptr, offsets);
+}
+at::Tensor grouped_gemv_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& s,
+                           const at::Tensor& offsets) {
+  return grouped_gemv_op<WE4m3>("grouped_gemv_w8", x, wq, &s, offsets);
 }
 
 }  // namespace spa
@@ -210,8 +336,12 @@ at::Tensor grouped_gemv(const at::Tensor& x, const at::Tensor& w, const at::Tens
 TORCH_LIBRARY_FRAGMENT(spa, m) {
   m.def("gemv(Tensor x, Tensor w) -> Tensor");
   m.def("grouped_gemv(Tensor x, Tensor w, Tensor offsets) -> Tensor");
+  m.def("gemv_w8(Tensor x, Tensor wq, Tensor s) -> Tensor");
+  m.def("grouped_gemv_w8(Tensor x, Tensor wq, Tensor s, Tensor offsets) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("gemv", &spa::gemv);
   m.impl("grouped_gemv", &spa::grouped_gemv);
+  m.impl("gemv_w8", &spa::gemv_w8);
+  m.impl("grouped_gemv_w8", &spa::grouped_gemv_w8);
 }

@@ -7,7 +7,7 @@
   prefill and decode separately;
 * :func:`quantize_decode_weights` / :func:`clear_decode_weights` -- fp8 weight-only decode:
   block-scaled e4m3 images of the projection matrices, read by the decode GEMV kernels
-  (csrc/kernels/gemv_w8.hip); see infer/quant.py.
+  (csrc/kernels/gemv.hip); see infer/quant.py.
 
 Reference entry points (all recompute the whole prefix per token, no cache):
 gpt/gpt-jax.ipynb:821-829, llama3/LLaMA-jax.ipynb:499-511, gemma/gemma.ipynb:608-630,

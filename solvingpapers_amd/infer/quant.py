@@ -6,7 +6,7 @@ parameter, the OCP e4m3 image with one E8M0 scale per 128 x 128 block -- the for
 training path (ops/moe.py ``quant_weight_fp8_blk``) and of DeepSeek-V3 checkpoints -- and
 attaches it to the Parameter. From then on decode-shaped inference products
 (``ops.linear.linear`` with <= 4 token rows, ``ops.moe.grouped_linear`` with <= 64 expert rows)
-read the image through ``gemv_w8`` / ``grouped_gemv_w8`` (csrc/kernels/gemv_w8.hip): half the
+read the image through ``gemv_w8`` / ``grouped_gemv_w8`` (csrc/kernels/gemv.hip): half the
 bytes per token.
 
 This mode buys decode speed and COSTS memory: the bf16 master weights stay (prefill, training

@@ -393,31 +393,35 @@ def _fp8_ok(x, w) -> bool:
             and w.shape[0] % 16 == 0 and K % 16 == 0 and x.numel() > 0 and (x.numel() // K) % 16 == 0)
 
 
+def _decode_linear(x, w, b):
+    """x w^T of a decode-shaped inference product on the weight-streaming GEMV, or None where the
+    product is not one. The weight's fp8 decode image where it carries one (``gemv_w8``; on the
+    CPU, :func:`_w8_cpu_ok`, the dequantised oracle product), else the bf16 master (``gemv``)."""
+    has_image = getattr(w, "_spa_w8", None) is not None
+    if _gemv_ok(x, w, b):
+        op = _ext.ops().gemv_w8 if has_image else _ext.ops().gemv
+    elif has_image and _w8_cpu_ok(x, w, b):
+        from .reference import gemv_w8 as op
+    else:
+        return None
+    from .moe import w8_image
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.stride(0) % 8:                          # the kernels read 16-byte aligned rows
+        x2 = x2.contiguous()
+    y = op(x2, *w8_image(w)) if has_image else op(x2, w)
+    return y.to(x.dtype).view(*x.shape[:-1], w.shape[0])
+
+
 def linear(x, w, b=None, fp8=False):
     """y = x w^T (+ b). ``fp8``: e4m3 forward / dX on hipBLASLt with row-wise scales (dims
-    multiples of 16; else bf16). A decode-shaped inference product whose weight carries an fp8
-    decode image (infer.quantize_decode_weights) reads the image (``gemv_w8``,
-    csrc/kernels/gemv_w8.hip; on the CPU the dequantised oracle product)."""
-    if getattr(w, "_spa_w8", None) is not None:
-        if _gemv_ok(x, w, b):
-            from .moe import w8_image
-            wq, s = w8_image(w)
-            x2 = x.reshape(-1, x.shape[-1])
-            if x2.stride(0) % 8:
-                x2 = x2.contiguous()
-            return _ext.ops().gemv_w8(x2, wq, s).view(*x.shape[:-1], w.shape[0])
-        if _w8_cpu_ok(x, w, b):
-            from .moe import w8_image
-            from .reference import gemv_w8
-            wq, s = w8_image(w)
-            return gemv_w8(x.reshape(-1, x.shape[-1]), wq, s).to(x.dtype).view(*x.shape[:-1], w.shape[0])
-    if fp8 and _fp8_ok(x, w) and not _gemv_ok(x, w, b):
+    multiples of 16; else bf16). A decode-shaped inference product goes to the GEMV kernels
+    (csrc/kernels/gemv.hip), ``fp8`` or not, and reads the weight's fp8 decode image
+    (infer.quantize_decode_weights) where it carries one (:func:`_decode_linear`)."""
+    y = _decode_linear(x, w, b)
+    if y is not None:
+        return y
+    if fp8 and _fp8_ok(x, w):
         return _LinearFP8Fn.apply(x, w, b)
-    if _gemv_ok(x, w, b):
-        x2 = x.reshape(-1, x.shape[-1])
-        if x2.stride(0) % 8:
-            x2 = x2.contiguous()
-        return _ext.ops().gemv(x2, w).view(*x.shape[:-1], w.shape[0])
     return _LinearFn.apply(x, w, b)
 
 

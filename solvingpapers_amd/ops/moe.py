@@ -272,18 +272,16 @@ def grouped_linear(xp, W, plan: MoEPlan, fp8: bool = False):
     active expert's weights once (``grouped_gemv``, csrc/kernels/gemv.hip) instead of paying a
     256-row MFMA tile per expert for one or two tokens. Where ``W`` carries an fp8 decode image
     (infer.quantize_decode_weights) that product reads the image instead
-    (``grouped_gemv_w8``, csrc/kernels/gemv_w8.hip; on the CPU the dequantised oracle product)."""
-    if not torch.is_grad_enabled() and xp.shape[0] <= GEMV_MAX_ROWS and getattr(W, "_spa_w8", None) is not None:
+    (``grouped_gemv_w8``, same file; on the CPU the dequantised oracle product)."""
+    if not torch.is_grad_enabled() and xp.shape[0] <= GEMV_MAX_ROWS:          # decode
+        has_image = getattr(W, "_spa_w8", None) is not None
         if xp.is_cuda and xp.dtype == torch.bfloat16 and W.dtype == torch.bfloat16:
-            wq, s = w8_image(W)
-            return ops().grouped_gemv_w8(xp.contiguous(), wq, s, plan.offsets)
-        if not xp.is_cuda:
+            if has_image:
+                return ops().grouped_gemv_w8(xp.contiguous(), *w8_image(W), plan.offsets)
+            return ops().grouped_gemv(xp.contiguous(), W.contiguous(), plan.offsets)
+        if has_image and not xp.is_cuda:
             from .reference import grouped_gemv_w8
-            wq, s = w8_image(W)
-            return grouped_gemv_w8(xp, wq, s, plan.offsets).to(xp.dtype)
-    if (xp.is_cuda and not torch.is_grad_enabled() and xp.shape[0] <= GEMV_MAX_ROWS
-            and xp.dtype == torch.bfloat16 and W.dtype == torch.bfloat16):
-        return ops().grouped_gemv(xp.contiguous(), W.contiguous(), plan.offsets)
+            return grouped_gemv_w8(xp, *w8_image(W), plan.offsets).to(xp.dtype)
     if fp8:
         return _GroupedLinearFP8Fn.apply(xp, W, plan)
     return _GroupedLinearFn.apply(xp, W, plan)

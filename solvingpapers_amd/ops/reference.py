@@ -198,7 +198,7 @@ def dequant_w8(wq, s):
 
 
 def gemv_w8(x, wq, s):
-    """x [M, K] times the dequantised image [N, K]^T, fp32 (csrc/kernels/gemv_w8.hip)."""
+    """x [M, K] times the dequantised image [N, K]^T, fp32 (csrc/kernels/gemv.hip)."""
     return x.float() @ dequant_w8(wq, s).t()
 
 

@@ -1,4 +1,4 @@
-"""Decode-path kernels: weight-streaming GEMV (csrc/kernels/gemv.hip) and the fused RoPE +
+"""Decode-path kernels: weight-streaming GEMV and grouped GEMV (csrc/kernels/gemv.hip) and the fused RoPE +
 KV-cache write (csrc/kernels/rope.hip, rope_kv_write_) against plain PyTorch fp32 / the
 unfused ops."""
 import pytest
@@ -40,6 +40,35 @@ def test_gemv_strided_rows():
     x = xb[:, :4096]
     w = torch.randn(1000, 4096, device=DEV, dtype=torch.bfloat16)
     assert rel(_ext.ops().gemv(x, w), x.float() @ w.float().t()) < 1e-2
+
+
+@pytest.mark.parametrize("N,K", [
+    (130, 136),           # N tail, K below one pass
+    (256, 2568),          # one unrolled pass, one single pass and a partial pass
+    (8197, 520),          # dense on RW = 4 with a ragged last wave, grouped on RW = 2
+])
+def test_grouped_gemv_one_expert_is_gemv_bitwise(N, K):
+    # dense and grouped are the same accumulation: same per-lane order, same reduction
+    torch.manual_seed(5)
+    w = torch.randn(N, K, device=DEV, dtype=torch.bfloat16)
+    for M in (1, 2, 3, 4):
+        x = torch.randn(M, K, device=DEV, dtype=torch.bfloat16)
+        off = torch.tensor([0, M], device=DEV, dtype=torch.int32)
+        assert torch.equal(_ext.ops().grouped_gemv(x, w[None], off), _ext.ops().gemv(x, w)), M
+
+
+def test_grouped_gemv_row_groups_are_gemv_bitwise():
+    # every expert's rows, in groups of at most 4 from its first row, against gemv on that expert's matrix
+    torch.manual_seed(6)
+    counts, N, K = [0, 1, 0, 5, 2, 0, 4, 0], 200, 264
+    w = torch.randn(len(counts), N, K, device=DEV, dtype=torch.bfloat16)
+    x = torch.randn(sum(counts), K, device=DEV, dtype=torch.bfloat16)
+    off = torch.tensor([0] + counts, dtype=torch.int32).cumsum(0)
+    y = _ext.ops().grouped_gemv(x, w, off.to(DEV, torch.int32))
+    for e, c in enumerate(counts):
+        for a in range(int(off[e]), int(off[e]) + c, 4):
+            b = min(a + 4, int(off[e + 1]))
+            assert torch.equal(y[a:b], _ext.ops().gemv(x[a:b], w[e])), (e, a, b)
 
 
 def test_linear_routes_decode_rows_to_gemv():

@@ -1,4 +1,4 @@
-"""fp8 weight-only decode on the GPU: gemv_w8 / grouped_gemv_w8 (csrc/kernels/gemv_w8.hip)
+"""fp8 weight-only decode on the GPU: gemv_w8 / grouped_gemv_w8 (csrc/kernels/gemv.hip)
 against the fp32 oracle on the dequantised image, their routing from linear / grouped_linear,
 and quantised models decoding token by token against the full forward of a copy that holds the
 dequantised weights.
@@ -95,6 +95,37 @@ def test_grouped_gemv_w8_matches_fp32_oracle():
     assert y.shape == (sum(counts), N) and y.dtype == torch.bfloat16
     print(f"grouped_gemv_w8: rel {rel(y, ref):.3e}")
     assert rel(y, ref) < 1e-2, rel(y, ref)
+
+
+@pytest.mark.parametrize("N,K", [
+    (128, 128),           # one block, 8 live lanes
+    (256, 5248),          # unrolled main loop, single-pass remainder and a partial pass
+    (8192, 256),          # dense on RW = 4, grouped on RW = 2
+])
+def test_grouped_gemv_w8_one_expert_is_gemv_w8_bitwise(N, K):
+    # dense and grouped are the same accumulation: same per-lane order, same reduction
+    wq, s = image(block_weights((N, K), 8))
+    assert len(torch.unique(s)) > 1 or s.numel() == 1
+    g = torch.Generator(DEV).manual_seed(9)
+    for M in (1, 2, 3, 4):
+        x = torch.randn(M, K, device=DEV, dtype=torch.bfloat16, generator=g)
+        off = torch.tensor([0, M], device=DEV, dtype=torch.int32)
+        assert torch.equal(_ext.ops().grouped_gemv_w8(x, wq[None], s[None], off), _ext.ops().gemv_w8(x, wq, s)), M
+
+
+def test_grouped_gemv_w8_row_groups_are_gemv_w8_bitwise():
+    # every expert's rows, in groups of at most 4 from its first row, against gemv_w8 on that expert's image
+    E, N, K = 8, 256, 384
+    counts = [0, 1, 0, 5, 2, 0, 4, 0]
+    wq, s = image(block_weights((E, N, K), 10))
+    assert len(torch.unique(s)) > 1
+    off = torch.tensor([0] + counts, dtype=torch.int32).cumsum(0)
+    x = torch.randn(sum(counts), K, device=DEV, dtype=torch.bfloat16, generator=torch.Generator(DEV).manual_seed(11))
+    y = _ext.ops().grouped_gemv_w8(x, wq, s, off.to(DEV, torch.int32))
+    for e, c in enumerate(counts):
+        for a in range(int(off[e]), int(off[e]) + c, 4):
+            b = min(a + 4, int(off[e + 1]))
+            assert torch.equal(y[a:b], _ext.ops().gemv_w8(x[a:b], wq[e], s[e])), (e, a, b)
 
 
 def test_linear_routes_decode_rows_to_gemv_w8():
