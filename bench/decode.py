@@ -4,7 +4,9 @@
 Default: LLaMA3-8B shape, bf16, random-init weights, synthetic prompt. Reports prefill
 tok/s and decode tok/s (all sequences); one JSON line. ``--weights fp8`` decodes from the
 block-scaled e4m3 images of infer.quantize_decode_weights (prefill stays on bf16). The
-reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
+``--sampler`` picks how the next token is drawn: ``greedy`` (argmax, captured with
+``--graph``), ``eager`` (infer.sample(): topk / sort / softmax / multinomial launches between the replays) or ``fused``
+(infer.Sampler: one kernel, captured in the graph). The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
 from __future__ import annotations
 
 import argparse
@@ -53,6 +55,12 @@ def main(argv=None):
     ap.add_argument("--set", action="append", default=[], help="config override key=value")
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: decode products read e4m3 weight images (128x128 E8M0 block scales)")
+    ap.add_argument("--sampler", choices=["greedy", "eager", "fused"], default="greedy",
+                    help="eager: infer.sample() between the steps; fused: infer.Sampler (one kernel, captured with --graph)")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
     m = build(a.model, a.layers, a.set).eval()
     extra = {}
@@ -63,20 +71,32 @@ def main(argv=None):
                  "quantized_params": len(rep["quantized"]), "bf16_params": len(rep["bf16"])}
     ids = torch.randint(0, m.c.vocab_size, (a.batch, a.prompt), device="cuda")
     st = GenerationStats()
+    from solvingpapers_amd.infer import Sampler
+    sampler = Sampler(a.temperature, a.top_k, a.top_p, seed=a.seed, device="cuda") if a.sampler == "fused" else None
+    # eager: today's sample() path with the same parameters, drawing from a seeded device generator
+    kw = {} if a.sampler != "eager" else {"temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
+                                          "generator": torch.Generator(device="cuda").manual_seed(a.seed)}
+    if a.sampler != "greedy":
+        extra.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)
     if a.graph:
         from solvingpapers_amd.infer import GraphDecoder
-        dec = GraphDecoder(m, a.batch, a.prompt + a.new)
-        dec.generate(ids[:, :64], 4)  # warm-up of the eager prefill path
-        out = dec.generate(ids, a.new, stats=st)
+        dec = GraphDecoder(m, a.batch, a.prompt + a.new, greedy=a.sampler == "greedy", sampler=sampler)
+        dec.generate(ids[:, :64], 4, **kw)  # warm-up of the eager prefill path
+        if sampler is not None:
+            sampler.reseed(a.seed)
+        out = dec.generate(ids, a.new, stats=st, **kw)
     else:
-        m.generate(ids[:, :64], 4, greedy=True)  # warm-up (kernels, allocator)
-        out = m.generate(ids, a.new, greedy=True, stats=st)
+        kw = dict(kw, greedy=a.sampler == "greedy", sampler=sampler)
+        m.generate(ids[:, :64], 4, **kw)  # warm-up (kernels, allocator)
+        if sampler is not None:
+            sampler.reseed(a.seed)
+        out = m.generate(ids, a.new, stats=st, **kw)
     torch.cuda.synchronize()
     print(json.dumps({"metric": "decode tokens/s", "model": a.model, "graph": a.graph, "batch": a.batch, "prompt": a.prompt,
                       "new_tokens": st.new_tokens, "prefill_tok_s": round(st.prefill_tok_s, 1),
                       "decode_tok_s": round(st.decode_tok_s, 2),
                       "ms_per_token": round(1e3 * st.decode_s / max(1, st.new_tokens // a.batch), 3),
-                      "dtype": "bf16", "data": "synthetic prompt, random-init weights",
+                      "dtype": "bf16", "data": "synthetic prompt, random-init weights", "sampler": a.sampler,
                       "out_len": out.shape[1], **extra}), flush=True)
 
 

@@ -14,19 +14,9 @@
 //  luong        global dot attention: w = softmax_s <st, h_s>, ctx = sum_s w h_s   K05
 //               attention/luong.ipynb:22-36
 #include "spa_common.h"
+#include "spa_rng.h"  // mix32 / u01 (shared with sample.hip)
 
 namespace spa {
-
-// --------------------------------------------------------------------------- RNG
-__device__ __forceinline__ uint32_t mix32(uint64_t k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return (uint32_t)k;
-}
-__device__ __forceinline__ float u01(uint64_t seed, uint64_t i) {  // (0, 1]
-  return ((float)(mix32(seed * 0x9E3779B97F4A7C15ULL + i) >> 8) + 1.f) * (1.f / 16777216.f);
-}
 
 // --------------------------------------------------------------------------- dropout
 // 8 elements per thread per step (16-byte bf16 / 2 x 16-byte fp32 vectors); the keep bit of

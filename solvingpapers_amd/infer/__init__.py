@@ -1,6 +1,8 @@
 """Inference: KV-cached generation for the language models of the catalogue.
 
 * :func:`sample` -- greedy / categorical / top-k / top-p with temperature;
+* :class:`Sampler` -- the same filters as one fused launch with a device-resident counter RNG
+  (csrc/kernels/sample.hip): reproducible, and capturable in the decode graph;
 * :class:`KVCache` -- preallocated per-layer K/V buffers, written in place;
 * :func:`generate` -- prompt prefill (flash attention) + token-by-token decode (split-K
   decode kernel, csrc/kernels/decode.hip) with the model's own cache layout, timing
@@ -17,7 +19,7 @@ from .cache import KVCache
 from .generate import GenerationStats, generate
 from .graph import DecodeState, GraphDecoder
 from .quant import clear_decode_weights, quantize_decode_weights
-from .sampling import sample
+from .sampling import Sampler, sample
 
-__all__ = ["KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "clear_decode_weights", "generate",
+__all__ = ["KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "Sampler", "clear_decode_weights", "generate",
            "quantize_decode_weights", "sample"]

@@ -50,9 +50,11 @@ def _sync(t: torch.Tensor):
 def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
              top_k: Optional[int] = None, top_p: Optional[float] = None, greedy: bool = False,
              eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-             stats: Optional[GenerationStats] = None, timed: bool = False) -> torch.Tensor:
+             stats: Optional[GenerationStats] = None, timed: bool = False, sampler=None) -> torch.Tensor:
     """ids [B, T0] -> [B, T0 + n] (n <= max_new_tokens; stops early once every sequence has
-    produced ``eos_token_id``, checked every 16 tokens to keep the host out of the loop)."""
+    produced ``eos_token_id``, checked every 16 tokens to keep the host out of the loop).
+    ``sampler`` (an infer.Sampler) replaces ``sample(...)``: one fused launch per token on the GPU,
+    the fp64 oracle on the CPU, both drawing u01(seed, call * B + row)."""
     was = model.training
     model.eval()
     timed = timed or stats is not None  # stats requested -> device-synchronised phase timings
@@ -81,7 +83,8 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
             st.prefill_s += t1 - t0
             n = 0
             while n < max_new_tokens:
-                nxt = sample(logits, temperature, top_k, greedy, generator, top_p)
+                nxt = sampler(logits) if sampler is not None else \
+                    sample(logits, temperature, top_k, greedy, generator, top_p)
                 if eos_token_id is not None:
                     nxt = torch.where(done[:, None], torch.full_like(nxt, eos_token_id), nxt)
                     done |= nxt[:, 0] == eos_token_id
@@ -103,7 +106,8 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
             for n in range(max_new_tokens):
                 window = out[:, -block:] if block else out
                 lg = model(window)[:, -1].float()
-                nxt = sample(lg, temperature, top_k, greedy, generator, top_p)
+                nxt = sampler(lg) if sampler is not None else \
+                    sample(lg, temperature, top_k, greedy, generator, top_p)
                 out = torch.cat([out, nxt], 1)
             if timed:
                 _sync(ids)

@@ -11,8 +11,11 @@ value on the device:
 
 The captured step ends by advancing that state on the device, and greedy sampling
 (argmax into the static token buffer) is captured too, so ``n`` tokens are ``n`` graph
-replays with no host work in between. Non-greedy sampling runs eagerly on the replay's
-logits between replays (torch.multinomial).
+replays with no host work in between. With a ``Sampler`` (infer/sampling.py) the captured step
+ends in the fused sampling kernel instead (temperature / top-k / top-p from a device-resident
+counter RNG, written into the same token buffer): non-greedy generation is ``n`` replays too.
+Without one, non-greedy sampling runs eagerly on the replay's logits between replays
+(torch.multinomial).
 
 Protocol a model implements: ``new_cache(B, max_len)``, ``step(ids, cache, pos)`` (eager
 prefill) and ``step_graph(ids, cache, state)`` (graph-safe decode step: no host syncs).
@@ -49,9 +52,10 @@ class DecodeState:
 
 
 class GraphDecoder:
-    def __init__(self, model, batch: int, max_len: int, greedy: bool = True, warmup: int = 2):
+    def __init__(self, model, batch: int, max_len: int, greedy: bool = True, warmup: int = 2, sampler=None):
         self.model, self.batch, self.max_len, self.greedy = model, batch, max_len, greedy
         dev = next(model.parameters()).device
+        self.sampler = sampler.to(dev) if sampler is not None else None
         self.cache = model.new_cache(batch, max_len)
         self.state = DecodeState(batch, max_len, dev)
         self.ids = torch.zeros(batch, 1, dtype=torch.long, device=dev)
@@ -60,7 +64,9 @@ class GraphDecoder:
 
     def _body(self):
         lg = self.model.step_graph(self.ids, self.cache, self.state)
-        if self.greedy:
+        if self.sampler is not None:
+            self.sampler(lg, out=self.ids)
+        elif self.greedy:
             self.ids.copy_(lg.argmax(-1, keepdim=True))
         self.state.advance()
         return lg
@@ -81,6 +87,8 @@ class GraphDecoder:
         with torch.cuda.graph(self.graph):
             self.logits = self._body()
         self.state.set(0)
+        if self.sampler is not None:   # the warm-up calls consumed offsets; the stream starts at 0
+            self.sampler.offset.zero_()
 
     @torch.no_grad()
     def prefill(self, ids: torch.Tensor) -> torch.Tensor:
@@ -97,6 +105,10 @@ class GraphDecoder:
     def generate(self, ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k=None,
                  top_p=None, generator=None, stats=None) -> torch.Tensor:
         import time
+        if self.sampler is not None and (temperature != 1.0 or top_k is not None or top_p is not None
+                                         or generator is not None):
+            raise ValueError("GraphDecoder: the captured sampler fixes temperature / top_k / top_p and draws from "
+                             "its own counter RNG; per-call sampling arguments cannot apply")
         if stats is not None:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -106,7 +118,9 @@ class GraphDecoder:
         t1 = time.perf_counter()
         n = min(max_new_tokens, self.max_len - ids.shape[1] + 1)
         out = torch.empty(self.batch, n, dtype=torch.long, device=ids.device)
-        if self.greedy:
+        if self.sampler is not None:
+            self.sampler(lg, out=self.ids)   # the first token: same kernel, next offset of the stream
+        elif self.greedy:
             self.ids.copy_(lg.argmax(-1, keepdim=True))
         else:
             self.ids.copy_(sample(lg, temperature, top_k, False, generator, top_p))
@@ -114,8 +128,8 @@ class GraphDecoder:
             out[:, i:i + 1].copy_(self.ids)
             if i + 1 == n:
                 break
-            self.graph.replay()  # feeds the token at row T0 + i; greedy leaves the next one in self.ids
-            if not self.greedy:
+            self.graph.replay()  # feeds the token at row T0 + i; greedy / the sampler leave the next one in self.ids
+            if self.sampler is None and not self.greedy:
                 self.ids.copy_(sample(self.logits, temperature, top_k, False, generator, top_p))
         if stats is not None:
             torch.cuda.synchronize()

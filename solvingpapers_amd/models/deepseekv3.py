@@ -899,12 +899,13 @@ class DeepSeekV3(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None):
         """Cached decoding (ref: one latent cache, Q1; mla: per-layer compressed cache).
         Reference sampling (deepseekv3.ipynb:1850-1873) recomputes the whole prefix per token
         with top-k + temperature; results are identical, the cache removes the recompute."""
         from ..infer.generate import generate
-        return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats)
+        return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
+                        sampler=sampler)
 
     # ------------------------------------------------------------------- metrics
     def num_params(self, active=False):

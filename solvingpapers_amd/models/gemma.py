@@ -555,10 +555,11 @@ class Gemma(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None):
         """KV-cached MQA decoding (the reference re-runs the window per token, gemma.ipynb:608-630)."""
         from ..infer.generate import generate
-        return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats)
+        return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
+                        sampler=sampler)
 
     def flops_per_token(self, T):
         c = self.c

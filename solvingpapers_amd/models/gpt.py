@@ -171,8 +171,8 @@ class GPT(tnn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, greedy=True, temperature=1.0, top_k=None, generator=None,
-                 eos_token_id=None, stats=None):
-        """gpt-jax.ipynb:821-829 (greedy by default). While prompt + new tokens fit the learned
+                 eos_token_id=None, stats=None, sampler=None):
+        """gpt-jax.ipynb:821-829 (greedy by default; ``sampler``: an infer.Sampler instead). While prompt + new tokens fit the learned
         position table (block_size) this is KV-cached: one prefill, then one token per step. Past
         block_size the reference crops the window to the last block_size tokens, which shifts
         every token's position embedding, so no cache can stand in: that tail re-forwards the
@@ -183,10 +183,12 @@ class GPT(tnn.Module):
         self.eval()
         n_cached = max(0, min(max_new_tokens, self.c.block_size - idx.shape[1]))
         if n_cached:
-            idx = generate(self, idx, n_cached, temperature, top_k, None, greedy, eos_token_id, generator, stats)
+            idx = generate(self, idx, n_cached, temperature, top_k, None, greedy, eos_token_id, generator, stats,
+                           sampler=sampler)
         for _ in range(max_new_tokens - n_cached):
             lg = self(idx[:, -self.c.block_size:])[:, -1].float()
-            idx = torch.cat([idx, sample(lg, temperature, top_k, greedy, generator)], 1)
+            nxt = sampler(lg) if sampler is not None else sample(lg, temperature, top_k, greedy, generator)
+            idx = torch.cat([idx, nxt], 1)
         self.train(was)
         return idx
 

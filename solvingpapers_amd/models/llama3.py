@@ -267,11 +267,12 @@ class Llama3(nn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None):
         """KV-cached sampling (reference: llama3/LLaMA-jax.ipynb:499-511, categorical at T=1,
         full re-forward per token; its cache path :816-819 was never exercised)."""
         from ..infer.generate import generate
-        return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats)
+        return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
+                        sampler=sampler)
 
     # ------------------------------------------------------- reference layout I/O
     def to_reference_params(self):

@@ -8,11 +8,12 @@ from .linear import Linear, linear
 from .moe import MoEPlan, combine, gather, grouped_gemm, grouped_linear, moe_ffn, permute, route
 from .norm import layer_norm, rms_norm
 from .rope import apply_rope, rope_packed_
+from .sampling import sample_logits, u01
 from .xent import cross_entropy, linear_cross_entropy, per_row_loss
 
 __all__ = [
     "act", "elu", "geglu", "gelu", "glu", "leaky_relu", "prelu", "relu", "sigmoid", "silu", "swiglu",
     "attention_packed", "decode_attention", "flash_attention", "embedding", "Linear", "linear", "layer_norm", "rms_norm",
     "apply_rope", "rope_packed_", "MoEPlan", "combine", "gather", "grouped_gemm", "grouped_linear", "moe_ffn",
-    "permute", "route", "cross_entropy", "linear_cross_entropy", "per_row_loss", "reference",
+    "permute", "route", "cross_entropy", "linear_cross_entropy", "per_row_loss", "reference", "sample_logits", "u01",
 ]

@@ -212,3 +212,34 @@ def grouped_gemv_w8(x, wq, s, offsets):
         if off[e + 1] > off[e]:
             out[off[e]:off[e + 1]] = x[off[e]:off[e + 1]].float() @ w[e].t()
     return out
+
+
+def sample_probs(logits, temperature=1.0, top_k=None, top_p=None):
+    """Unnormalised fp64 sampling weights [B, V] in vocabulary order (0 for dropped tokens): the
+    distribution csrc/kernels/sample.hip draws from. Order: raw logit descending, ties by ascending
+    token index (stable sort); top-k keeps the first k of that order (None, 0 or >= V: off); top-p
+    keeps a token iff the softmax(logit / T) mass -- renormalised on what top-k kept -- strictly
+    before it in the order is <= top_p (None or >= 1: off), so the first token always stays: today's
+    infer.sampling._nucleus on today's sample() path. -inf has weight 0."""
+    x = logits.detach().double()
+    V = x.shape[-1]
+    T = max(float(temperature), 1e-6)
+    xs, idx = torch.sort(x, dim=-1, descending=True, stable=True)
+    e = torch.exp((xs - xs[:, :1]) / T)
+    if top_k is not None and 1 <= int(top_k) < V:
+        e[:, int(top_k):] = 0.0
+    if top_p is not None and float(top_p) < 1.0:
+        p = e / e.sum(-1, keepdim=True)
+        before = p.cumsum(-1) - p
+        e = torch.where(before <= float(top_p), e, torch.zeros_like(e))
+    return torch.zeros_like(e).scatter_(1, idx, e)
+
+
+def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, u=None):
+    """logits [B, V], u [B] in (0, 1] -> token ids [B, 1] (int64): with P = sample_probs(...), C its
+    inclusive prefix sum in vocabulary order and Z = C[:, -1], the smallest i with C[i] >= u * Z.
+    fp64 throughout. u carries 24 bits (ops.sampling.u01), so a token with less than 2^-24 of the kept
+    mass may never be drawn. Rows holding NaN, or nothing finite, are unspecified."""
+    C = sample_probs(logits, temperature, top_k, top_p).cumsum(-1)
+    target = u.detach().double().reshape(-1, 1) * C[:, -1:]
+    return (C < target).sum(-1, keepdim=True).clamp_(max=C.shape[-1] - 1)

@@ -4,7 +4,8 @@ as achieved HBM bandwidth (ideal bytes / time). Run under ``rocprofv3 --pmc`` fo
 usage: python tools/bench_kernels.py [--iters N] [--only name,name]
 
 ``--only gemv`` runs just the decode GEMV rows: the fp8 weight-only kernel (gemv_w8) against the bf16
-kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4.
+kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only sample`` runs just the
+token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
 """
 import argparse
 import json
@@ -139,6 +140,35 @@ def gemv_rows(iters, rounds=3):
         del wb, wf
 
 
+def sample_rows(iters, rounds=3):
+    """The fused sampler (csrc/kernels/sample.hip) beside infer.sample() on the same logits: V = 128256,
+    fp32 holding bf16-rounded values as step_graph hands them over, arms alternated A B B A per round,
+    medians. ``fused_graph_ms`` is one HIP-graph replay of the op plus the offset increment (how
+    GraphDecoder runs it); ``fused_ms`` and ``eager_ms`` are host-enqueued, as between two replays."""
+    from solvingpapers_amd.infer import Sampler, sample
+    V = 128256
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for B in (1, 4, 16):
+        lg = (torch.randn(B, V, device=DEV, generator=g) * 2).bfloat16().float()
+        ids = torch.zeros(B, 1, dtype=torch.long, device=DEV)
+        for name, k, p in (("plain", None, None), ("top_k50", 50, None), ("top_p0.9", None, 0.9), ("top_k50_p0.9", 50, 0.9)):
+            smp = Sampler(0.8, k, p, seed=1, device=DEV)
+            gen = torch.Generator(device=DEV).manual_seed(1)
+            arms = {"fused_graph": _graphed(lambda: smp(lg, out=ids)),
+                    "fused": lambda: smp(lg, out=ids),
+                    "eager": lambda: ids.copy_(sample(lg, 0.8, k, False, gen, p))}
+            ms = {a: [] for a in arms}
+            for _ in range(rounds):
+                for arm in ("eager", "fused", "fused_graph", "fused_graph", "fused", "eager"):
+                    ms[arm].append(timed(arms[arm], iters))
+            med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+            print(json.dumps({"kernel": f"sample_{name}_B{B}_V{V}", "fused_graph_ms": round(med["fused_graph"], 5),
+                              "fused_ms": round(med["fused"], 5), "eager_ms": round(med["eager"], 5),
+                              "fused_graph_vs_eager": round(med["fused_graph"] / med["eager"], 3),
+                              "min_ms": {a: round(min(v), 5) for a, v in ms.items()},
+                              "max_ms": {a: round(max(v), 5) for a, v in ms.items()}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -148,7 +178,9 @@ def main():
     only = set(filter(None, a.only.split(",")))
     if not only or "gemv" in only:
         gemv_rows(a.iters)
-    for name, (fn, nbytes) in ({} if only == {"gemv"} else cases()).items():
+    if not only or "sample" in only:
+        sample_rows(a.iters)
+    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample"} else cases()).items():
         if only and name not in only:
             continue
         ms = timed(fn, a.iters)
