@@ -3,7 +3,9 @@
 
 Default: LLaMA3-8B shape, bf16, random-init weights, synthetic prompt. Reports prefill
 tok/s and decode tok/s (all sequences); one JSON line. ``--weights fp8`` decodes from the
-block-scaled e4m3 images of infer.quantize_decode_weights (prefill stays on bf16). The
+block-scaled e4m3 images of infer.quantize_decode_weights (prefill stays on bf16);
+``--kv-cache fp8`` keeps the KV cache as e4m3 rows with per-row E8M0 scales (infer/cache.py) and
+decodes with attn_decode_q8 -- the cache's size is reported as ``kv_cache_bytes`` either way. The
 ``--sampler`` picks how the next token is drawn: ``greedy`` (argmax, captured with
 ``--graph``), ``eager`` (infer.sample(): topk / sort / softmax / multinomial launches between the replays) or ``fused``
 (infer.Sampler: one kernel, captured in the graph). The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
@@ -55,6 +57,8 @@ def main(argv=None):
     ap.add_argument("--set", action="append", default=[], help="config override key=value")
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: decode products read e4m3 weight images (128x128 E8M0 block scales)")
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: e4m3 KV cache with one E8M0 scale per (batch, kv head, token) row")
     ap.add_argument("--sampler", choices=["greedy", "eager", "fused"], default="greedy",
                     help="eager: infer.sample() between the steps; fused: infer.Sampler (one kernel, captured with --graph)")
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -69,6 +73,8 @@ def main(argv=None):
         rep = quantize_decode_weights(m)
         extra = {"weights": rep["format"], "image_bytes": rep["image_bytes"],
                  "quantized_params": len(rep["quantized"]), "bf16_params": len(rep["bf16"])}
+    kvc = None if a.kv_cache == "bf16" else a.kv_cache     # None: every call as before the option existed
+    ckw = {} if kvc is None else {"kv_cache": kvc}
     ids = torch.randint(0, m.c.vocab_size, (a.batch, a.prompt), device="cuda")
     st = GenerationStats()
     from solvingpapers_amd.infer import Sampler
@@ -80,13 +86,16 @@ def main(argv=None):
         extra.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)
     if a.graph:
         from solvingpapers_amd.infer import GraphDecoder
-        dec = GraphDecoder(m, a.batch, a.prompt + a.new, greedy=a.sampler == "greedy", sampler=sampler)
+        dec = GraphDecoder(m, a.batch, a.prompt + a.new, greedy=a.sampler == "greedy", sampler=sampler, **ckw)
+        cache_bytes = dec.cache.nbytes() if hasattr(dec.cache, "nbytes") else None
         dec.generate(ids[:, :64], 4, **kw)  # warm-up of the eager prefill path
         if sampler is not None:
             sampler.reseed(a.seed)
         out = dec.generate(ids, a.new, stats=st, **kw)
     else:
-        kw = dict(kw, greedy=a.sampler == "greedy", sampler=sampler)
+        kw = dict(kw, greedy=a.sampler == "greedy", sampler=sampler, **ckw)
+        row = m.new_cache(a.batch, 1, **ckw)     # generate() allocates prompt + new rows of this size
+        cache_bytes = row.nbytes() * (a.prompt + a.new) if hasattr(row, "nbytes") else None
         m.generate(ids[:, :64], 4, **kw)  # warm-up (kernels, allocator)
         if sampler is not None:
             sampler.reseed(a.seed)
@@ -97,6 +106,7 @@ def main(argv=None):
                       "decode_tok_s": round(st.decode_tok_s, 2),
                       "ms_per_token": round(1e3 * st.decode_s / max(1, st.new_tokens // a.batch), 3),
                       "dtype": "bf16", "data": "synthetic prompt, random-init weights", "sampler": a.sampler,
+                      "kv_cache": a.kv_cache, "kv_cache_bytes": cache_bytes,
                       "out_len": out.shape[1], **extra}), flush=True)
 
 

@@ -17,10 +17,15 @@
 //   behind SPA_DECODE_FUSED=1: its cross-XCD release/acquire fences measured slower).
 // Causal: query row t sits at position Tk - Tq + t (the cache holds the prefix plus the new
 // tokens); keys beyond a row's position are masked.
+// attn_decode_q8 (second half of the file) is the same scheme over an fp8 (e4m3 + per-row E8M0
+// scale) KV cache.
 #include "spa_common.h"
+#include "fp8_quant.h"
 
 #include <map>
 #include <mutex>
+
+SPA_DEBUG_TU("decode.hip")
 
 namespace spa {
 
@@ -370,9 +375,302 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k, co
   return {out, lse};
 }
 
+// ------------------------------------------------------------------ fp8 KV cache
+// The same split-K scheme over an e4m3 cache (infer/cache.py quant="fp8"; written by rope.hip's
+// kv_quant_write_ / rope_kv_write_q8_): K / V rows are e4m3 bytes [B, Tk, Hkv, hd], each with one E8M0
+// scale byte per (b, kv head, token) in [B, Hkv, Tk], token-contiguous, so a block reads its scales
+// as one byte run. A row's scale is common to its hd values, so it never touches the inner loops: the
+// K scale multiplies the fp32 score after the dot, the V scale multiplies p (l sums the unscaled
+// p); q stays fp32 (q * scale_log2 is not rounded). Every dequantised product is exact in fp32.
+//
+// A kernel of its own, not a cache-format policy on attn_decode_kernel: the lane mapping differs (VPL
+// below changes the lanes per key, the groups per block and the register arrays' shapes), and the
+// bf16 instantiations stay byte for byte what they were.
+//
+// VPL = head-dim values (= bytes) per lane per key:
+//   R = 4, 8:  VPL 8 -- 8-byte loads, the bf16 kernel's access width, hd / 8 lanes per key and twice the
+//              keys per wave step; o / qv double to [R][8] (R = 8: 128 VGPRs for the two), which fits.
+//   R = 16:    VPL 4 -- the bf16 lane mapping with 4-byte loads. o / qv at [16][8] would be 256 VGPRs
+//              before any load is in flight; and 16 rows are 4096 FMAs per 2 * hd cache bytes, which
+//              is VALU-bound on this chip at either load width (~39 T FMA/s against ~31 G keys/s of
+//              hd-128 e4m3 rows from HBM), so the narrower loads are not what limits it.
+struct DecodeQ8Params {
+  DecodeParams d;  // k / v point at e4m3 bytes; strides in bytes
+  const uint8_t* ks; const uint8_t* vs;
+  long ksb, ksh, vsb, vsh;
+};
+
+constexpr int q8_vpl(int R) { return R <= 8 ? 8 : 4; }
+constexpr int q8_keys_per_batch(int hd, int vpl) { return 4 * (64 / (hd / vpl)) * kKeysPerLoad; }
+
+template <int VPL>
+struct Q8Row;  // VPL e4m3 bytes of one cache row
+template <>
+struct Q8Row<4> {
+  unsigned w;
+  __device__ __forceinline__ void load(const uint8_t* p) { w = *reinterpret_cast<const unsigned*>(p); }
+  __device__ __forceinline__ void unpack(float (&f)[4]) const {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+  }
+};
+template <>
+struct Q8Row<8> {
+  uint2 w;
+  __device__ __forceinline__ void load(const uint8_t* p) { w = *reinterpret_cast<const uint2*>(p); }
+  __device__ __forceinline__ void unpack(float (&f)[8]) const {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
+    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
+    f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+    f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+  }
+};
+
+template <int HD, int R>
+__global__ __launch_bounds__(256) void attn_decode_q8_kernel(DecodeQ8Params pp) {
+  const DecodeParams& p = pp.d;
+  constexpr int VPL = q8_vpl(R);
+  constexpr int KL = HD / VPL;      // lanes per key
+  constexpr int KPW = 64 / KL;      // keys per wave step
+  constexpr int NG = 4 * KPW;       // lane groups per block
+  constexpr int KPL = kKeysPerLoad; // keys per lane group per load batch
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sub = lane % KL, grp = wave * KPW + lane / KL;
+  const int bh = blockIdx.x, split = blockIdx.y;
+  const int hk = bh % p.Hkv, b = bh / p.Hkv;
+  const int G = p.H / p.Hkv;
+  const int rows = G * p.Tq;
+  const int Tk = p.kv_len ? min(*p.kv_len, p.Tk) : p.Tk;
+  const int k0 = split * p.chunk, k1 = min(Tk, k0 + p.chunk);
+
+  // query slices (pre-scaled to log2 units, fp32), rows r = t * G + g  (head hk*G + g, token t)
+  float qv[R][VPL];
+  int qpos[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int t = r / G, g = r % G;
+    qpos[r] = p.causal ? Tk - p.Tq + t : Tk;
+    if (r < rows) {
+      const bf16* qp = p.q + b * p.sqb + (long)t * p.sqt + (long)(hk * G + g) * p.sqh + VPL * sub;
+#pragma unroll
+      for (int j4 = 0; j4 < VPL; j4 += 4) {
+        const bf16x4 x = *reinterpret_cast<const bf16x4*>(qp + j4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) qv[r][j4 + j] = (float)x[j] * p.scale_log2;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) qv[r][j] = 0.f;
+      qpos[r] = -1;  // never visible
+    }
+  }
+  float m[R], l[R], o[R][VPL];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -INFINITY; l[r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) o[r][j] = 0.f;
+  }
+  const uint8_t* kb = reinterpret_cast<const uint8_t*>(p.k) + b * p.skb + hk * p.skh + VPL * sub;
+  const uint8_t* vb = reinterpret_cast<const uint8_t*>(p.v) + b * p.svb + hk * p.svh + VPL * sub;
+  const uint8_t* ksb = pp.ks + b * pp.ksb + hk * pp.ksh;
+  const uint8_t* vsb = pp.vs + b * pp.vsb + hk * pp.vsh;
+  // load batches as in attn_decode_kernel: 2 * KPL row loads and 2 * KPL scale bytes in flight per lane
+  for (int base = k0; base < k1; base += NG * KPL) {
+    Q8Row<VPL> kx[KPL], vx[KPL];
+    unsigned ksc[KPL], vsc[KPL];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      const long kk = min(base + j * NG + grp, k1 - 1);
+      SPA_DBG_CHECK(kk, p.Tk);  // cache row and scale index (debug build)
+      kx[j].load(kb + kk * p.skt);
+      vx[j].load(vb + kk * p.svt);
+      ksc[j] = ksb[kk];
+      vsc[j] = vsb[kk];
+    }
+    // the rows stay packed in registers and are converted at each use, as the bf16 kernel does with
+    // its bf16 pairs (v_cvt_pk_f32_fp8: one VALU op per two values, against one per value there)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s[KPL];
+      float mx = m[r];
+#pragma unroll
+      for (int j = 0; j < KPL; ++j) {
+        float kf[VPL];
+        kx[j].unpack(kf);
+        float d = qv[r][0] * kf[0];
+#pragma unroll
+        for (int e = 1; e < VPL; ++e) d = fmaf(qv[r][e], kf[e], d);
+#pragma unroll
+        for (int w = KL / 2; w > 0; w >>= 1) d += __shfl_xor(d, w, KL);
+        const int key = base + j * NG + grp;
+        s[j] = (key >= k1 || key > qpos[r]) ? -INFINITY : d * e8m0_val(ksc[j]);
+        mx = fmaxf(mx, s[j]);
+      }
+      if (mx == -INFINITY) continue;  // nothing visible yet for this row
+      const float alpha = __builtin_amdgcn_exp2f(m[r] - mx);  // m = -inf -> 0
+      l[r] *= alpha;
+#pragma unroll
+      for (int e = 0; e < VPL; ++e) o[r][e] *= alpha;
+#pragma unroll
+      for (int j = 0; j < KPL; ++j) {
+        const float pj = __builtin_amdgcn_exp2f(s[j] - mx);
+        l[r] += pj;
+        const float pv = pj * e8m0_val(vsc[j]);
+        float vf[VPL];
+        vx[j].unpack(vf);
+#pragma unroll
+        for (int e = 0; e < VPL; ++e) o[r][e] = fmaf(pv, vf[e], o[r][e]);
+      }
+      m[r] = mx;
+    }
+  }
+  // merge the NG lane groups: in-wave groups through shuffles, then waves through LDS
+  __shared__ float sm[4][R], sl[4][R], so[4][R][HD];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int w = KL; w < 64; w <<= 1) {
+      const float m2 = __shfl_xor(m[r], w, 64), l2 = __shfl_xor(l[r], w, 64);
+      const float mn = fmaxf(m[r], m2);
+      const float a1 = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[r] - mn);
+      const float a2 = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
+      l[r] = l[r] * a1 + l2 * a2;
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) o[r][j] = o[r][j] * a1 + __shfl_xor(o[r][j], w, 64) * a2;
+      m[r] = mn;
+    }
+    if (lane < KL) {
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) so[wave][r][VPL * sub + j] = o[r][j];
+      if (sub == 0) { sm[wave][r] = m[r]; sl[wave][r] = l[r]; }
+    }
+  }
+  __syncthreads();
+  // rows x hd outputs of this split: thread -> (row, 4-element slice); attn_decode_combine_kernel
+  // merges the splits
+  constexpr int S4 = HD / 4;
+  for (int i = tid; i < rows * S4; i += 256) {
+    const int r = i / S4, s4 = i % S4;
+    float mn = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mn = fmaxf(mn, sm[w][r]);
+    float lt = 0.f, ot[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float a = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sm[w][r] - mn);
+      lt += sl[w][r] * a;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ot[j] += so[w][r][4 * s4 + j] * a;
+    }
+    const int t = r / G, hq = hk * G + r % G;
+    const long row = (((long)split * p.B + b) * p.Tq + t) * p.H + hq;
+    SPA_DBG_CHECK(row, (long)p.nsplit * p.B * p.Tq * p.H);
+    f32x4 w4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w4[j] = ot[j];
+    *reinterpret_cast<f32x4*>(p.opart + row * HD + 4 * s4) = w4;
+    if (s4 == 0) { p.mpart[row] = mn; p.lpart[row] = lt; }
+  }
+}
+
+// attn_decode over the fp8 cache: q bf16 [B, Tq, H, hd]; kq / vq float8_e4m3fn [B, Tk, Hkv, hd] and
+// ks / vs uint8 E8M0 [B, Hkv, Tk] (views of the cache buffers; with kv_len the whole buffers).
+// Same contract and return as attn_decode.
+std::vector<at::Tensor> attn_decode_q8(const at::Tensor& q, const at::Tensor& kq, const at::Tensor& ks,
+                                       const at::Tensor& vq, const at::Tensor& vs, double scale, bool causal,
+                                       int64_t nsplit_req, const c10::optional<at::Tensor>& kv_len) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.dim() == 4, "attn_decode_q8: q must be bf16 [B,T,H,hd]");
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(2) % 4 == 0 && q.stride(1) % 4 == 0 && q.stride(0) % 4 == 0 &&
+                  ((uintptr_t)q.data_ptr() % 8) == 0,
+              "attn_decode_q8: q rows must be 8-byte aligned and contiguous in hd");
+  const int B = q.size(0), Tq = q.size(1), H = q.size(2), HD = q.size(3);
+  for (auto* t : {&kq, &vq}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat8_e4m3fn && t->dim() == 4,
+                "attn_decode_q8: the cache must be float8_e4m3fn [B,Tk,Hkv,hd]");
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) % 8 == 0 && t->stride(1) % 8 == 0 && t->stride(0) % 8 == 0 &&
+                    ((uintptr_t)t->data_ptr() % 8) == 0,
+                "attn_decode_q8: cache rows must be 8-byte aligned and contiguous in hd");
+  }
+  const int Tk = kq.size(1), Hkv = kq.size(2);
+  TORCH_CHECK(kq.size(0) == B && vq.size(0) == B && vq.size(1) == Tk && vq.size(2) == Hkv && kq.size(3) == HD &&
+              vq.size(3) == HD && Hkv > 0 && H % Hkv == 0, "attn_decode_q8: shape mismatch");
+  for (auto* t : {&ks, &vs})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kByte && t->dim() == 3 && t->size(0) == B && t->size(1) == Hkv &&
+                    t->size(2) == Tk && t->stride(2) == 1,
+                "attn_decode_q8: scales must be uint8 [B, Hkv, Tk], token-contiguous");
+  TORCH_CHECK(Tq <= Tk, "attn_decode_q8: the cache must hold the query tokens");
+  const int rows = Tq * (H / Hkv);
+  TORCH_CHECK(rows <= kMaxRows, "attn_decode_q8: Tq * H / Hkv must be <= 16 (dequantise and use flash attention for prefill)");
+  TORCH_CHECK(HD == 64 || HD == 128 || HD == 256, "attn_decode_q8: head dim must be 64, 128 or 256");
+  DeviceGuard g(q.device());
+  auto out = at::empty({B, Tq, H, HD}, q.options());
+  auto lse = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
+  if (B * Tq * H == 0) return {out, lse};
+  const int R = rows <= 4 ? 4 : rows <= 8 ? 8 : 16;
+  // Split granule: half a load batch (4 of the 8 keys per lane group). With 8 values per lane a whole
+  // batch is twice the bf16 kernel's keys, and whole-batch splits gave a short cache half as many blocks
+  // (batch 1, 1K tokens, hd 128: 64 blocks, 14.8 us against the bf16 kernel's 128 blocks and 11.5 us);
+  // a half-filled batch costs the same one round trip.
+  const int kpb = q8_keys_per_batch(HD, q8_vpl(R)) / 2;
+  int nsplit = (int)nsplit_req;
+  int chunk;
+  if (nsplit <= 0) {  // as attn_decode: the grid covers the chip ~2x, each split whole granules
+    const int want = std::max(1, 512 / std::max(1, B * Hkv));
+    nsplit = std::max(1, std::min(want, cdiv(Tk, kpb)));
+    chunk = cdiv(cdiv(Tk, nsplit), kpb) * kpb;
+  } else {
+    chunk = cdiv(Tk, nsplit);
+  }
+  nsplit = cdiv(Tk, chunk);
+  auto part = at::empty({(long)nsplit * B * Tq * H * (HD + 2)}, q.options().dtype(at::kFloat));
+  DecodeQ8Params pp{};
+  DecodeParams& p = pp.d;
+  p.q = (const bf16*)q.data_ptr(); p.k = (const bf16*)kq.data_ptr(); p.v = (const bf16*)vq.data_ptr();
+  pp.ks = (const uint8_t*)ks.data_ptr(); pp.vs = (const uint8_t*)vs.data_ptr();
+  pp.ksb = ks.stride(0); pp.ksh = ks.stride(1); pp.vsb = vs.stride(0); pp.vsh = vs.stride(1);
+  p.opart = part.data_ptr<float>();
+  p.mpart = p.opart + (long)nsplit * B * Tq * H * HD;
+  p.lpart = p.mpart + (long)nsplit * B * Tq * H;
+  p.out = (bf16*)out.data_ptr(); p.lse = lse.data_ptr<float>();
+  p.B = B; p.Tq = Tq; p.Tk = Tk; p.H = H; p.Hkv = Hkv; p.nsplit = nsplit; p.chunk = chunk;
+  p.sqb = q.stride(0); p.sqt = q.stride(1); p.sqh = q.stride(2);
+  p.skb = kq.stride(0); p.skt = kq.stride(1); p.skh = kq.stride(2);
+  p.svb = vq.stride(0); p.svt = vq.stride(1); p.svh = vq.stride(2);
+  p.sob = out.stride(0); p.sot = out.stride(1); p.soh = out.stride(2);
+  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  p.causal = causal;
+  if (kv_len.has_value()) {  // the whole cache; the valid length lives on the device
+    TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
+                "attn_decode_q8: kv_len must be a device int32 tensor");
+    p.kv_len = kv_len->data_ptr<int>();
+  }
+  auto st = stream();
+  const dim3 grid(B * Hkv, nsplit);
+  const int nrows = B * Tq * H;
+#define SPA_DECODE_Q8_LAUNCH(HDV)                                                                   \
+  {                                                                                                \
+    if (R == 4) attn_decode_q8_kernel<HDV, 4><<<grid, 256, 0, st>>>(pp);                           \
+    else if (R == 8) attn_decode_q8_kernel<HDV, 8><<<grid, 256, 0, st>>>(pp);                      \
+    else attn_decode_q8_kernel<HDV, 16><<<grid, 256, 0, st>>>(pp);                                 \
+    attn_decode_combine_kernel<HDV><<<nrows, 256, 0, st>>>(p);                                     \
+  }
+  if (HD == 64) SPA_DECODE_Q8_LAUNCH(64)
+  else if (HD == 128) SPA_DECODE_Q8_LAUNCH(128)
+  else SPA_DECODE_Q8_LAUNCH(256)
+#undef SPA_DECODE_Q8_LAUNCH
+  SPA_LAUNCH_CHECK();
+  return {out, lse};
+}
+
 }  // namespace spa
 
 TORCH_LIBRARY_FRAGMENT(spa, m) {
   m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, bool causal, int nsplit, Tensor? kv_len=None) -> Tensor[]");
+  m.def("attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, float scale, bool causal, int nsplit, "
+        "Tensor? kv_len=None) -> Tensor[]");
 }
-TORCH_LIBRARY_IMPL(spa, CUDA, m) { m.impl("attn_decode", &spa::attn_decode); }
+TORCH_LIBRARY_IMPL(spa, CUDA, m) {
+  m.impl("attn_decode", &spa::attn_decode);
+  m.impl("attn_decode_q8", &spa::attn_decode_q8);
+}

@@ -20,6 +20,7 @@
 // k-step. Per-expert row offsets on the device (block-scan tile -> expert map, as in
 // moe.hip), XCD-remapped tile order.
 #include "spa_common.h"
+#include "fp8_quant.h"
 
 SPA_DEBUG_TU("moe_fp8.hip")
 
@@ -63,26 +64,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16* __restr
 // 1 x 128 tiles, weights in 128 x 128 blocks, each with a power-of-two (E8M0) scale 2^e chosen as
 // the smallest with amax / 2^e <= 448. The GEMM hands the E8M0 bytes straight to
 // v_mfma_scale_f32_32x32x64_f8f6f4, so the accumulation over differently scaled k-blocks happens
-// inside the MFMA in fp32 -- no per-block promotion pass.
-__device__ __forceinline__ int e8m0_exp(float amax) {       // e with amax / 2^e <= 448, minimal
-  if (!(amax > 0.f)) return 0;
-  const unsigned b = __float_as_uint(amax * (1.f / 448.f));
-  int e = (int)((b >> 23) & 0xff) - 127;
-  if (b & 0x7fffff) ++e;                                     // round the power up
-  return max(-126, min(127, e));
-}
-__device__ __forceinline__ float e8m0_inv(int e) { return __uint_as_float((unsigned)(127 - e) << 23); }
-__device__ __forceinline__ int2 q8(const float (&v)[8], float inv) {
-  float w[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) w[i] = fminf(fmaxf(v[i] * inv, -448.f), 448.f);
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(w[0], w[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(w[2], w[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(w[4], w[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(w[6], w[7], hi, true);
-  return make_int2(lo, hi);
-}
+// inside the MFMA in fp32 -- no per-block promotion pass. e8m0_exp / e8m0_inv / q8: fp8_quant.h.
 
 // x [R, K] bf16 -> q [R, K] e4m3, s [R, K/128] E8M0; 16 lanes per 128-wide tile, one read of x
 __global__ __launch_bounds__(256) void quant_act_blk_kernel(const bf16* __restrict__ x, uint8_t* __restrict__ q,

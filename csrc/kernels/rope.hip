@@ -10,7 +10,10 @@
 // Layout: each thread owns 8 contiguous bf16 of one head row (16-byte load/store);
 // cos/sin come from an fp32 table [Tmax, hd/2] (L2/LLC resident).
 #include "spa_common.h"
+#include "fp8_quant.h"
 #include <type_traits>
+
+SPA_DEBUG_TU("rope.hip")
 
 namespace spa {
 
@@ -228,6 +231,218 @@ void rope_kv_write_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor
   SPA_LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------ fp8 KV cache writers
+// Cache format (infer/cache.py, quant="fp8"): K and V rows as OCP e4m3 bytes [B, Tmax, Hkv, hd] (the
+// bf16 cache's layout) plus one E8M0 scale byte per (batch, kv head, token) in [B, Hkv, Tmax]; a row
+// is x ~= q * 2^(s - 127) with the fp8_quant.h scale choice over the row's hd values. What is quantised
+// is the bf16 value the bf16 cache would hold, so "fp8 cache == torch-quantise(bf16 cache)" bitwise.
+struct KV8Dst {
+  uint8_t* q; uint8_t* s;
+  long qb, qt, qh;  // byte strides of the e4m3 rows (hd contiguous)
+  long sb, sh;      // scale strides (token contiguous)
+};
+
+// Eager write: bf16 k / v [B, T, Hkv, hd] (strided views of the packed qkv buffer) into cache rows
+// [pos, pos + T). hd / 8 adjacent lanes own one (k|v, b, t, head) row: 8 values each, amax by
+// shuffles inside the lane group, then the scale, the bytes and the scale byte; the row is read once.
+__global__ __launch_bounds__(256) void kv_quant_write_kernel(const bf16* __restrict__ k, const bf16* __restrict__ v,
+                                                             KV8Dst kd, KV8Dst vd, long skb, long skt, long skh,
+                                                             long svb, long svt, long svh, int B, int T, int Hkv,
+                                                             int hd, int pos, int Tmax) {
+  const int vpr = hd / 8;  // lanes per row: a power of two <= 64, so a lane group never straddles a wave
+  const long total = 2L * B * T * Hkv * vpr;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int l = i % vpr;
+    long r = i / vpr;
+    const int h = r % Hkv;
+    r /= Hkv;
+    const int t = r % T;
+    r /= T;
+    const int b = r % B;
+    const bool isv = r / B != 0;
+    const bf16* src = isv ? v + b * svb + t * svt + h * svh : k + b * skb + t * skt + h * skh;
+    const KV8Dst& d = isv ? vd : kd;
+    float a[8];
+    load8(src + l * 8, a);
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(a[j]));
+    for (int o = 1; o < vpr; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const int e = e8m0_exp(amax);
+    const long row = (long)pos + t;
+    if (SPA_DBG_OK(row, Tmax)) {
+      *reinterpret_cast<int2*>(d.q + b * d.qb + row * d.qt + h * d.qh + l * 8) = q8(a, e8m0_inv(e));
+      if (l == 0 && SPA_DBG_OK(h * (long)Tmax + row, (long)Hkv * Tmax)) d.s[b * d.sb + h * d.sh + row] = (uint8_t)(e + 127);
+    }
+  }
+}
+
+// e4m3 data [B, Tmax, Hkv, hd] + E8M0 scales [B, Hkv, Tmax] of one cache side, checked
+static KV8Dst kv8_dst(const at::Tensor& q, const at::Tensor& s, int64_t B, int64_t Hkv, int64_t hd, const char* op) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 4 && q.stride(3) == 1,
+              op, ": cache data must be float8_e4m3fn [B, Tmax, Hkv, hd] with contiguous hd");
+  TORCH_CHECK(q.size(0) == B && q.size(2) == Hkv && q.size(3) == hd, op, ": cache shape mismatch");
+  TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 && q.stride(2) % 8 == 0 && (uintptr_t)q.data_ptr() % 8 == 0,
+              op, ": 8-byte aligned cache rows");
+  TORCH_CHECK(s.is_cuda() && s.scalar_type() == at::kByte && s.dim() == 3 && s.size(0) == B && s.size(1) == Hkv &&
+                  s.size(2) == q.size(1) && s.stride(2) == 1,
+              op, ": scales must be uint8 [B, Hkv, Tmax], token-contiguous");
+  return KV8Dst{(uint8_t*)q.data_ptr(), (uint8_t*)s.data_ptr(), q.stride(0), q.stride(1), q.stride(2), s.stride(0),
+                s.stride(1)};
+}
+
+void kv_quant_write_(const at::Tensor& k, const at::Tensor& v, const at::Tensor& kq, const at::Tensor& ks,
+                     const at::Tensor& vq, const at::Tensor& vs, int64_t pos) {
+  for (auto* t : {&k, &v}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->dim() == 4 && t->stride(3) == 1,
+                "kv_quant_write: bf16 [B, T, Hkv, hd] k / v with contiguous hd");
+    TORCH_CHECK(t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0 &&
+                    (uintptr_t)t->data_ptr() % 16 == 0,
+                "kv_quant_write: 16-byte aligned rows");
+  }
+  const int B = k.size(0), T = k.size(1), Hkv = k.size(2), hd = k.size(3);
+  TORCH_CHECK(v.sizes() == k.sizes(), "kv_quant_write: k / v shape mismatch");
+  TORCH_CHECK(hd >= 8 && hd <= 512 && (hd & (hd - 1)) == 0, "kv_quant_write: hd must be a power of two in [8, 512]");
+  const KV8Dst kd = kv8_dst(kq, ks, B, Hkv, hd, "kv_quant_write"), vd = kv8_dst(vq, vs, B, Hkv, hd, "kv_quant_write");
+  const int Tmax = kq.size(1);
+  TORCH_CHECK(vq.size(1) == Tmax, "kv_quant_write: cache shape mismatch");
+  TORCH_CHECK(pos >= 0 && pos + T <= Tmax, "kv_quant_write: rows [", pos, ", ", pos + T, ") outside a ", Tmax, "-row cache");
+  DeviceGuard g(k.device());
+  const long total = 2L * B * T * Hkv * (hd / 8);
+  if (total == 0) return;
+  const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  kv_quant_write_kernel<<<grid, 256, 0, stream()>>>((const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(), kd, vd,
+                                                    k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
+                                                    v.stride(2), B, T, Hkv, hd, (int)pos, Tmax);
+  SPA_LAUNCH_CHECK();
+}
+
+// rope_kv_write_ for the fp8 cache (graph decode prologue): the q heads are rotated in place exactly
+// as there; a k head is rotated, rounded to bf16 (the value the bf16 cache would hold) and quantised, a
+// v head is quantised, both into row *index + t. The hd / 8 threads of a head row are adjacent lanes
+// in this index mapping, so the row's amax is a shuffle reduction among them (rotate_half: the upper
+// half of the lanes holds no data and contributes 0).
+template <int MODE>
+__global__ __launch_bounds__(256) void rope_kv_write_q8_kernel(bf16* __restrict__ x, const float* __restrict__ cosT,
+                                                               const float* __restrict__ sinT,
+                                                               const int* __restrict__ pos,
+                                                               const long* __restrict__ index, KV8Dst kd, KV8Dst vd,
+                                                               long sb, long st, long sh, int B, int T, int H, int Hkv,
+                                                               int hd, int Tmax) {
+  const int vpr = hd / 8;
+  const int NH = H + 2 * Hkv;
+  const long total = (long)B * T * NH * vpr;
+  const long row0 = *index;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int v = i % vpr;
+    long r = i / vpr;
+    const int hh = r % NH;
+    r /= NH;
+    const int t = r % T;
+    const int b = r / T;
+    const long row = row0 + t;
+    if (hh >= H && (row >= Tmax || row < 0)) continue;  // whole lane groups: hh and row are uniform in a row
+    bf16* src = x + b * sb + t * st + hh * sh;
+    float a[8], bq[8];
+    bool lo = true, hi = false;  // this lane holds elements [8v, 8v+8) / also their partners at +hd/2
+    if (hh >= H + Hkv) {         // v: as is
+      load8(src + v * 8, a);
+    } else {
+      const int ps = pos[b * T + t];
+      const float* c = cosT + (long)ps * (hd / 2);
+      const float* s = sinT + (long)ps * (hd / 2);
+      if constexpr (MODE == 0) {
+        load8(src + v * 8, a);
+        const f32x4 cv = *reinterpret_cast<const f32x4*>(c + v * 4);
+        const f32x4 sv = *reinterpret_cast<const f32x4*>(s + v * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float x0 = a[2 * k], x1 = a[2 * k + 1];
+          a[2 * k] = fmaf(x0, cv[k], -(x1 * sv[k]));
+          a[2 * k + 1] = fmaf(x0, sv[k], x1 * cv[k]);
+        }
+      } else {  // rotate_half: thread v < vpr/2 owns elements [8v, 8v+8) and their partners at +hd/2
+        lo = hi = v < vpr / 2;
+        if (lo) {
+          float cv[8], sv[8];
+          load8(src + v * 8, a);
+          load8(src + hd / 2 + v * 8, bq);
+          load8(c + v * 8, cv);
+          load8(s + v * 8, sv);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float x0 = a[k], x1 = bq[k];
+            a[k] = fmaf(x0, cv[k], -(x1 * sv[k]));
+            bq[k] = fmaf(x0, sv[k], x1 * cv[k]);
+          }
+        }
+      }
+      if (hh < H) {  // q: in place
+        if (lo) store8(src + v * 8, a);
+        if (hi) store8(src + hd / 2 + v * 8, bq);
+        continue;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {  // k: the bf16 the bf16 cache would hold
+        a[k] = (float)(bf16)a[k];
+        bq[k] = (float)(bf16)bq[k];
+      }
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (lo) amax = fmaxf(amax, fabsf(a[k]));
+      if (hi) amax = fmaxf(amax, fabsf(bq[k]));
+    }
+    for (int o = 1; o < vpr; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const int e = e8m0_exp(amax);
+    const float inv = e8m0_inv(e);
+    const bool isv = hh >= H + Hkv;
+    const int h = hh - H - (isv ? Hkv : 0);
+    const KV8Dst& d = isv ? vd : kd;
+    if (!SPA_DBG_OK(row, Tmax)) continue;
+    uint8_t* dst = d.q + b * d.qb + row * d.qt + h * d.qh;
+    if (lo) *reinterpret_cast<int2*>(dst + v * 8) = q8(a, inv);
+    if (hi) *reinterpret_cast<int2*>(dst + hd / 2 + v * 8) = q8(bq, inv);
+    if (v == 0 && SPA_DBG_OK(h * (long)Tmax + row, (long)Hkv * Tmax)) d.s[b * d.sb + h * d.sh + row] = (uint8_t)(e + 127);
+  }
+}
+
+void rope_kv_write_q8_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                       const at::Tensor& index, const at::Tensor& kq, const at::Tensor& ks, const at::Tensor& vq,
+                       const at::Tensor& vs, int64_t H, int64_t Hkv, int64_t mode) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 && x.stride(3) == 1,
+              "rope_kv_write_q8: bf16 [B, T, heads, hd] qkv with contiguous hd");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(1) % 8 == 0 && x.stride(2) % 8 == 0 && (uintptr_t)x.data_ptr() % 16 == 0,
+              "rope_kv_write_q8: 16-byte aligned rows");
+  const int B = x.size(0), T = x.size(1), hd = x.size(3);
+  TORCH_CHECK(x.size(2) == H + 2 * Hkv && hd >= 16 && hd <= 512 && (hd & (hd - 1)) == 0,
+              "rope_kv_write_q8: x must be packed [B, T, H + 2 Hkv, hd], hd a power of two in [16, 512]");
+  const KV8Dst kd = kv8_dst(kq, ks, B, Hkv, hd, "rope_kv_write_q8"), vd = kv8_dst(vq, vs, B, Hkv, hd, "rope_kv_write_q8");
+  TORCH_CHECK(vq.size(1) == kq.size(1), "rope_kv_write_q8: cache shape mismatch");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.is_contiguous() && sin.is_contiguous() && cos.size(1) == hd / 2,
+              "rope_kv_write_q8: fp32 [Tmax, hd/2] tables");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == (int64_t)B * T,
+              "rope_kv_write_q8: pos must be device int32 [B, T]");
+  TORCH_CHECK(index.is_cuda() && index.scalar_type() == at::kLong && index.numel() >= 1,
+              "rope_kv_write_q8: index must be a device int64 tensor");
+  TORCH_CHECK(mode == 0 || mode == 1, "rope_kv_write_q8: mode 0 (interleaved) or 1 (rotate_half)");
+  DeviceGuard g(x.device());
+  const long total = (long)B * T * (H + 2 * Hkv) * (hd / 8);
+  if (total == 0) return;
+  const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  auto launch = [&](auto modec) {
+    constexpr int M = decltype(modec)::value;
+    rope_kv_write_q8_kernel<M><<<grid, 256, 0, stream()>>>(
+        (bf16*)x.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(),
+        index.data_ptr<int64_t>(), kd, vd, x.stride(0), x.stride(1), x.stride(2), B, T, (int)H, (int)Hkv, hd,
+        (int)kq.size(1));
+  };
+  if (mode == 0) launch(std::integral_constant<int, 0>{});
+  else launch(std::integral_constant<int, 1>{});
+  SPA_LAUNCH_CHECK();
+}
+
 }  // namespace spa
 
 TORCH_LIBRARY_FRAGMENT(spa, m) {
@@ -235,8 +450,13 @@ TORCH_LIBRARY_FRAGMENT(spa, m) {
         "bool inverse) -> ()");
   m.def("rope_kv_write_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kc, "
         "Tensor(c!) vc, int n_heads, int n_kv_heads, int mode=0) -> ()");
+  m.def("kv_quant_write_(Tensor k, Tensor v, Tensor(a!) kq, Tensor(b!) ks, Tensor(c!) vq, Tensor(d!) vs, int pos) -> ()");
+  m.def("rope_kv_write_q8_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kq, "
+        "Tensor(c!) ks, Tensor(d!) vq, Tensor(e!) vs, int n_heads, int n_kv_heads, int mode=0) -> ()");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("rope_", &spa::rope_);
   m.impl("rope_kv_write_", &spa::rope_kv_write_);
+  m.impl("kv_quant_write_", &spa::kv_quant_write_);
+  m.impl("rope_kv_write_q8_", &spa::rope_kv_write_q8_);
 }

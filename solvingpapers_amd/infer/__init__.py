@@ -3,7 +3,9 @@
 * :func:`sample` -- greedy / categorical / top-k / top-p with temperature;
 * :class:`Sampler` -- the same filters as one fused launch with a device-resident counter RNG
   (csrc/kernels/sample.hip): reproducible, and capturable in the decode graph;
-* :class:`KVCache` -- preallocated per-layer K/V buffers, written in place;
+* :class:`KVCache` -- preallocated per-layer K/V buffers, written in place; ``quant="fp8"`` (the
+  drivers' ``kv_cache="fp8"``, one of :data:`KV_CACHE_FORMATS`) keeps them as e4m3 rows with per-row
+  E8M0 scales, one :class:`KV8` handle per layer, read by the fp8 decode-attention kernel;
 * :func:`generate` -- prompt prefill (flash attention) + token-by-token decode (split-K
   decode kernel, csrc/kernels/decode.hip) with the model's own cache layout, timing
   prefill and decode separately;
@@ -15,11 +17,12 @@ Reference entry points (all recompute the whole prefix per token, no cache):
 gpt/gpt-jax.ipynb:821-829, llama3/LLaMA-jax.ipynb:499-511, gemma/gemma.ipynb:608-630,
 deepseekv3/deepseekv3.ipynb:1849-1873.
 """
-from .cache import KVCache
+from ..ops.attention import KV8
+from .cache import KV_CACHE_FORMATS, KVCache
 from .generate import GenerationStats, generate
 from .graph import DecodeState, GraphDecoder
 from .quant import clear_decode_weights, quantize_decode_weights
 from .sampling import Sampler, sample
 
-__all__ = ["KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "Sampler", "clear_decode_weights", "generate",
+__all__ = ["KV8", "KV_CACHE_FORMATS", "KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "Sampler", "clear_decode_weights", "generate",
            "quantize_decode_weights", "sample"]

@@ -50,11 +50,14 @@ def _sync(t: torch.Tensor):
 def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
              top_k: Optional[int] = None, top_p: Optional[float] = None, greedy: bool = False,
              eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-             stats: Optional[GenerationStats] = None, timed: bool = False, sampler=None) -> torch.Tensor:
+             stats: Optional[GenerationStats] = None, timed: bool = False, sampler=None,
+             kv_cache: Optional[str] = None) -> torch.Tensor:
     """ids [B, T0] -> [B, T0 + n] (n <= max_new_tokens; stops early once every sequence has
     produced ``eos_token_id``, checked every 16 tokens to keep the host out of the loop).
     ``sampler`` (an infer.Sampler) replaces ``sample(...)``: one fused launch per token on the GPU,
-    the fp64 oracle on the CPU, both drawing u01(seed, call * B + row)."""
+    the fp64 oracle on the CPU, both drawing u01(seed, call * B + row).
+    ``kv_cache="fp8"`` decodes from an e4m3 KV cache (infer/cache.py; models with ``new_cache(...,
+    kv_cache=)``); None / "bf16": the model-dtype cache."""
     was = model.training
     model.eval()
     timed = timed or stats is not None  # stats requested -> device-synchronised phase timings
@@ -70,7 +73,7 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
             if limit is not None:
                 total = min(total, limit)
             prompt = ids[:, -total:] if T0 > total else ids
-            cache = model.new_cache(B, total)
+            cache = model.new_cache(B, total) if kv_cache is None else model.new_cache(B, total, kv_cache=kv_cache)
             if timed:
                 _sync(ids)
             t0 = time.perf_counter()
@@ -101,6 +104,8 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
             st.decode_s += time.perf_counter() - t1
             st.new_tokens += B * n
         else:
+            if kv_cache not in (None, "bf16"):
+                raise NotImplementedError(f"kv_cache={kv_cache!r} needs a model with the cached-decoding protocol")
             block = limit or getattr(getattr(model, "c", None), "block_size", None)
             t1 = time.perf_counter()
             for n in range(max_new_tokens):

@@ -52,11 +52,14 @@ class DecodeState:
 
 
 class GraphDecoder:
-    def __init__(self, model, batch: int, max_len: int, greedy: bool = True, warmup: int = 2, sampler=None):
+    def __init__(self, model, batch: int, max_len: int, greedy: bool = True, warmup: int = 2, sampler=None,
+                 kv_cache: Optional[str] = None):
         self.model, self.batch, self.max_len, self.greedy = model, batch, max_len, greedy
         dev = next(model.parameters()).device
         self.sampler = sampler.to(dev) if sampler is not None else None
-        self.cache = model.new_cache(batch, max_len)
+        # kv_cache="fp8": the captured step quantises its K/V row and attends over e4m3 rows
+        self.cache = model.new_cache(batch, max_len) if kv_cache is None else \
+            model.new_cache(batch, max_len, kv_cache=kv_cache)
         self.state = DecodeState(batch, max_len, dev)
         self.ids = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.logits: Optional[torch.Tensor] = None

@@ -866,8 +866,12 @@ class DeepSeekV3(tnn.Module):
         return c.mtp_lambda * tot / max(1, len(self.mtp_layers))
 
     # ---------------------------------------------------------------- inference
-    def new_cache(self, B, Tmax):
+    def new_cache(self, B, Tmax, kv_cache=None):
         c = self.c
+        if kv_cache not in (None, "bf16"):
+            raise NotImplementedError(f"kv_cache={kv_cache!r}: the fp8 KV cache covers the GQA / MQA K/V caches; "
+                                      "DeepSeek-V3 caches MLA latents (one compressed row per token), which it "
+                                      "does not quantise")
         dev, dt = self.embed.device, self.embed.dtype
         if c.attention == "ref":
             return [torch.zeros(B, Tmax, c.latent_dim, device=dev, dtype=dt)]
@@ -899,13 +903,13 @@ class DeepSeekV3(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None, sampler=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None):
         """Cached decoding (ref: one latent cache, Q1; mla: per-layer compressed cache).
         Reference sampling (deepseekv3.ipynb:1850-1873) recomputes the whole prefix per token
         with top-k + temperature; results are identical, the cache removes the recompute."""
         from ..infer.generate import generate
         return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
-                        sampler=sampler)
+                        sampler=sampler, kv_cache=kv_cache)
 
     # ------------------------------------------------------------------- metrics
     def num_params(self, active=False):

@@ -27,9 +27,9 @@ import torch.nn as tnn
 
 from .. import nn as snn
 from ..infer.graph import DecodeState
-from ..ops import _ext, attention_packed, embedding, glu, linear, linear_cross_entropy, rms_norm, rope_packed_
+from ..ops import attention_packed, embedding, glu, linear, linear_cross_entropy, rms_norm, rope_packed_
 from ..ops.linear import swiglu_mlp
-from ..ops.attention import decode_attention, flash_attention
+from ..ops.attention import flash_attention, kv_cache_attend, kv_cache_write, rope_kv_cache_write_
 from ..ops.linear import linear_rows
 from ..ops.misc import dropout
 from ..ops.rope import RopeCache, gemma_ref_rotate
@@ -265,10 +265,10 @@ class GemmaBlock(tnn.Module):
         if isinstance(pos, DecodeState):  # graph-capturable decode step: positions on the device
             x4 = qkv.view(B, T, self.hl + 2 * KV, hd)
             cos, sin = RopeCache.get(pos.max_len, hd, c.rope_theta, qkv.device)
-            kc, vc = cache
-            # one launch: rotate_half RoPE on q (in place) and k, k/v rows into the cache
-            _ext.ops().rope_kv_write_(x4, cos, sin, pos.positions, pos.index, kc, vc, self.hl, KV, 1)
-            o = decode_attention(x4[:, :, :self.hl], kc, vc, causal=True, kv_len=pos.kv_len)
+            # one launch: rotate_half RoPE on q (in place) and k, k/v rows into the cache (an fp8
+            # cache: quantised on the way, and read by the e4m3 decode kernel)
+            rope_kv_cache_write_(cache, x4, cos, sin, pos.positions, pos.index, self.hl, KV, 1)
+            o = kv_cache_attend(x4[:, :, :self.hl], cache, causal=True, kv_len=pos.kv_len)
             a = reduce_from_tp(linear(o.reshape(B, T, self.hl * hd), self.wo), tp_group)
             n2, h2 = rms_norm(a, self.ffn_norm, c.norm_eps, residual=h)
             f = glu(linear(copy_to_tp(n2, tp_group), self.w13), "gelu_tanh")
@@ -278,10 +278,9 @@ class GemmaBlock(tnn.Module):
             o = attention_packed(qkv, self.hl, KV, causal=True, head_dim=hd)
         else:  # KV-cached inference: write this step's K/V, attend over the cache
             x4 = qkv.view(B, T, self.hl + 2 * KV, hd)
-            kc, vc = cache
-            kc[:, pos:pos + T] = x4[:, :, self.hl:self.hl + KV]
-            vc[:, pos:pos + T] = x4[:, :, self.hl + KV:]
-            o = decode_attention(x4[:, :, :self.hl], kc[:, :pos + T], vc[:, :pos + T], causal=True)
+            k, v = x4[:, :, self.hl:self.hl + KV], x4[:, :, self.hl + KV:]
+            kv_cache_write(cache, k, v, pos)
+            o = kv_cache_attend(x4[:, :, :self.hl], cache, pos + T, causal=True, fresh=(k, v) if pos == 0 else None)
             o = o.reshape(B, T, self.hl * hd)
         a = reduce_from_tp(linear(o, self.wo), tp_group)
         n2, h2 = rms_norm(a, self.ffn_norm, c.norm_eps, residual=h)
@@ -534,10 +533,12 @@ class Gemma(tnn.Module):
     def max_context(self):
         return self.c.max_seq_len
 
-    def new_cache(self, B, Tmax):
-        from ..infer.cache import KVCache
+    def new_cache(self, B, Tmax, kv_cache=None):
+        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py)."""
+        from ..infer.cache import KVCache, kv_cache_quant
         c = self.c
-        return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.embed.device, dtype=self.embed.dtype)
+        return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.embed.device, dtype=self.embed.dtype,
+                       quant=kv_cache_quant(kv_cache))
 
     def step(self, ids, cache, pos):
         from ..parallel.tensor_parallel import gather_vocab_logits
@@ -555,11 +556,11 @@ class Gemma(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None, sampler=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None):
         """KV-cached MQA decoding (the reference re-runs the window per token, gemma.ipynb:608-630)."""
         from ..infer.generate import generate
         return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
-                        sampler=sampler)
+                        sampler=sampler, kv_cache=kv_cache)
 
     def flops_per_token(self, T):
         c = self.c

@@ -23,7 +23,7 @@ import torch.nn as tnn
 
 from .. import nn as snn
 from ..ops import act, attention_packed, embedding, layer_norm, linear, linear_cross_entropy
-from ..ops.attention import attention_dropout, decode_attention
+from ..ops.attention import attention_dropout, kv_cache_attend, kv_cache_write
 from ..ops.misc import dropout
 from ..utils.grad import mark_ready
 
@@ -84,10 +84,9 @@ class Block(tnn.Module):
             # single tokens, flash for the prompt (ops/attention.py decode_attention)
             H = c.num_heads
             q4 = qkv.view(B, T, 3 * H, hd)
-            kc, vc = cache
-            kc[:, pos:pos + T] = q4[:, :, H:2 * H]
-            vc[:, pos:pos + T] = q4[:, :, 2 * H:]
-            o = decode_attention(q4[:, :, :H], kc[:, :pos + T], vc[:, :pos + T], causal=True)
+            k, v = q4[:, :, H:2 * H], q4[:, :, 2 * H:]
+            kv_cache_write(cache, k, v, pos)
+            o = kv_cache_attend(q4[:, :, :H], cache, pos + T, causal=True, fresh=(k, v) if pos == 0 else None)
             return self.proj(o.reshape(B, T, D))
         p = c.dropout_rate if self.training else 0.0
         if p > 0:
@@ -157,11 +156,12 @@ class GPT(tnn.Module):
     def max_context(self):
         return self.c.block_size
 
-    def new_cache(self, B, Tmax):
-        from ..infer.cache import KVCache
+    def new_cache(self, B, Tmax, kv_cache=None):
+        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py)."""
+        from ..infer.cache import KVCache, kv_cache_quant
         c = self.c
         return KVCache(c.num_layers, B, Tmax, c.num_heads, c.emb_dim // c.num_heads,
-                       device=self.token_embed.device, dtype=self.token_embed.dtype)
+                       device=self.token_embed.device, dtype=self.token_embed.dtype, quant=kv_cache_quant(kv_cache))
 
     def step(self, ids, cache, pos):
         """Write ids' K/V at cache rows [pos, pos+T) (learned positions pos..pos+T-1), return the
@@ -171,12 +171,13 @@ class GPT(tnn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, greedy=True, temperature=1.0, top_k=None, generator=None,
-                 eos_token_id=None, stats=None, sampler=None):
+                 eos_token_id=None, stats=None, sampler=None, kv_cache=None):
         """gpt-jax.ipynb:821-829 (greedy by default; ``sampler``: an infer.Sampler instead). While prompt + new tokens fit the learned
         position table (block_size) this is KV-cached: one prefill, then one token per step. Past
         block_size the reference crops the window to the last block_size tokens, which shifts
         every token's position embedding, so no cache can stand in: that tail re-forwards the
-        cropped window exactly as the reference does."""
+        cropped window exactly as the reference does. ``kv_cache="fp8"``: the cached part decodes from an
+        e4m3 cache."""
         from ..infer.generate import generate
         from ..infer.sampling import sample
         was = self.training
@@ -184,7 +185,7 @@ class GPT(tnn.Module):
         n_cached = max(0, min(max_new_tokens, self.c.block_size - idx.shape[1]))
         if n_cached:
             idx = generate(self, idx, n_cached, temperature, top_k, None, greedy, eos_token_id, generator, stats,
-                           sampler=sampler)
+                           sampler=sampler, kv_cache=kv_cache)
         for _ in range(max_new_tokens - n_cached):
             lg = self(idx[:, -self.c.block_size:])[:, -1].float()
             nxt = sampler(lg) if sampler is not None else sample(lg, temperature, top_k, greedy, generator)

@@ -25,12 +25,12 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from ..infer.cache import KVCache
+from ..infer.cache import KVCache, kv_cache_quant
 from ..infer.graph import DecodeState
 from ..infer.sampling import sample  # noqa: F401  (re-exported: reference-style sampling)
-from ..ops import _ext, attention_packed, embedding, linear, linear_cross_entropy, rms_norm, rope_packed_
+from ..ops import attention_packed, embedding, linear, linear_cross_entropy, rms_norm, rope_packed_
 from ..ops.linear import swiglu_mlp
-from ..ops.attention import decode_attention
+from ..ops.attention import kv_cache_attend, kv_cache_write, rope_kv_cache_write_
 from ..ops.rope import RopeCache, apply_rope
 from ..utils.grad import mark_ready
 
@@ -112,10 +112,10 @@ class LlamaBlock(nn.Module):
             H, KV = c.n_heads, c.n_kv_heads
             x4 = qkv.view(B, T, H + 2 * KV, hd)
             cos, sin = RopeCache.get(pos.max_len, hd, c.rope_theta, qkv.device, c.ref_freqs)
-            kc, vc = kv_cache
-            # one launch: RoPE on q (in place) and k, k/v rows into the cache at pos.index
-            _ext.ops().rope_kv_write_(x4, cos, sin, pos.positions, pos.index, kc, vc, H, KV, 0)
-            o = decode_attention(x4[:, :, :H], kc, vc, causal=True, kv_len=pos.kv_len)
+            # one launch: RoPE on q (in place) and k, k/v rows into the cache at pos.index (an fp8
+            # cache: quantised on the way, and read by the e4m3 decode kernel)
+            rope_kv_cache_write_(kv_cache, x4, cos, sin, pos.positions, pos.index, H, KV, 0)
+            o = kv_cache_attend(x4[:, :, :H], kv_cache, causal=True, kv_len=pos.kv_len)
             return linear(o.reshape(B, T, H * hd), self.wo)
         if kv_cache is None and self.cp_group is not None:
             # sequence slice at offset rank*T: RoPE at global positions, attention over all
@@ -135,11 +135,10 @@ class LlamaBlock(nn.Module):
             q = apply_rope(qkv[:, :, :c.n_heads], c.rope_theta, pos, ref_freqs=c.ref_freqs)
             k = apply_rope(qkv[:, :, c.n_heads:c.n_heads + c.n_kv_heads], c.rope_theta, pos, ref_freqs=c.ref_freqs)
             v = qkv[:, :, c.n_heads + c.n_kv_heads:]
-            kc, vc = kv_cache
-            kc[:, pos:pos + T] = k
-            vc[:, pos:pos + T] = v
-            # decode steps: split-K decode kernel; prompt prefill: flash (decode_attention routes)
-            o = decode_attention(q, kc[:, :pos + T], vc[:, :pos + T], causal=True)
+            kv_cache_write(kv_cache, k, v, pos)
+            # decode steps: split-K decode kernel; prompt prefill: flash (decode_attention routes);
+            # an fp8 cache attends a prompt at position 0 over its fresh k / v
+            o = kv_cache_attend(q, kv_cache, pos + T, causal=True, fresh=(k, v) if pos == 0 else None)
         return linear(o.reshape(B, T, c.n_heads * hd), self.wo)
 
     def forward(self, res, delta, kv_cache=None, pos=0):
@@ -247,10 +246,12 @@ class Llama3(nn.Module):
     def max_context(self):
         return self.c.max_seq_len
 
-    def new_cache(self, B, Tmax):
+    def new_cache(self, B, Tmax, kv_cache=None):
+        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py); None / "bf16": the
+        model-dtype cache."""
         c = self.c
         return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.tok_embeddings.device,
-                       dtype=self.tok_embeddings.dtype)
+                       dtype=self.tok_embeddings.dtype, quant=kv_cache_quant(kv_cache))
 
     def step(self, ids, cache, pos):
         """Write ids' K/V at cache rows [pos, pos+T), return the last position's logits [B, V]."""
@@ -267,12 +268,12 @@ class Llama3(nn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None, sampler=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None):
         """KV-cached sampling (reference: llama3/LLaMA-jax.ipynb:499-511, categorical at T=1,
         full re-forward per token; its cache path :816-819 was never exercised)."""
         from ..infer.generate import generate
         return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
-                        sampler=sampler)
+                        sampler=sampler, kv_cache=kv_cache)
 
     # ------------------------------------------------------- reference layout I/O
     def to_reference_params(self):

@@ -440,6 +440,116 @@ def decode_attention(q, k, v, causal=True, scale=None, nsplit=0, kv_len=None):
     return flash_attention(q.contiguous(), k, v, causal, scale)
 
 
+# ------------------------------------------------------------------ KV-cache layers (bf16 pair | fp8)
+class KV8:
+    """One layer of an fp8 KV cache (infer/cache.py ``quant="fp8"``): ``kq`` / ``vq`` float8_e4m3fn
+    [B, Tmax, Hkv, hd] (the bf16 cache's layout) and ``ks`` / ``vs`` uint8 E8M0 scales [B, Hkv, Tmax],
+    one per (batch, kv head, token) over the row's hd values: x ~= q * 2^(s - 127)
+    (reference.quant_kv8). ``dtype`` is the model's (what dequantised rows are returned in)."""
+    __slots__ = ("kq", "ks", "vq", "vs", "dtype")
+
+    def __init__(self, kq, ks, vq, vs, dtype=torch.bfloat16):
+        self.kq, self.ks, self.vq, self.vs, self.dtype = kq, ks, vq, vs, dtype
+
+    @classmethod
+    def zeros(cls, batch, max_len, n_kv_heads, head_dim, device=None, dtype=torch.bfloat16):
+        q = lambda: torch.zeros(batch, max_len, n_kv_heads, head_dim, device=device, dtype=torch.uint8) \
+            .view(torch.float8_e4m3fn)
+        s = lambda: torch.zeros(batch, n_kv_heads, max_len, device=device, dtype=torch.uint8)
+        return cls(q(), s(), q(), s(), dtype)
+
+    @property
+    def max_len(self):
+        return self.kq.shape[1]
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.kq, self.ks, self.vq, self.vs))
+
+    def dequantized(self, n):
+        """(k, v) rows [0, n) in the model dtype (every value exact in bf16)."""
+        return (reference.dequant_kv8(self.kq[:, :n], self.ks, self.dtype),
+                reference.dequant_kv8(self.vq[:, :n], self.vs, self.dtype))
+
+
+def _kv8_write_ok(k, v):
+    hd = k.shape[-1]
+    return (k.is_cuda and k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16 and 8 <= hd <= 512
+            and hd & (hd - 1) == 0
+            and all(t.stride(3) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(2) % 8 == 0
+                    and t.data_ptr() % 16 == 0 for t in (k, v)))
+
+
+def kv_cache_write(cache, k, v, pos):
+    """Store this step's k / v [B, T, Hkv, hd] at cache rows [pos, pos+T). ``cache``: a bf16
+    ``(kc, vc)`` pair (two slice copies, as the models always did) or a :class:`KV8` layer (bf16 on
+    the GPU: the quantising kv_quant_write_ kernel, one launch for both; else the torch formula)."""
+    T = k.shape[1]
+    if not isinstance(cache, KV8):
+        kc, vc = cache
+        kc[:, pos:pos + T] = k
+        vc[:, pos:pos + T] = v
+        return
+    if pos < 0 or pos + T > cache.max_len:
+        raise ValueError(f"KV cache overflow: rows [{pos}, {pos + T}) of {cache.max_len}")
+    if _kv8_write_ok(k, v):
+        _ext.ops().kv_quant_write_(k, v, cache.kq, cache.ks, cache.vq, cache.vs, int(pos))
+        return
+    for x, q, s in ((k, cache.kq, cache.ks), (v, cache.vq, cache.vs)):
+        xq, xs = reference.quant_kv8(x)
+        q.view(torch.uint8)[:, pos:pos + T] = xq.view(torch.uint8)
+        s[:, :, pos:pos + T] = xs
+
+
+def rope_kv_cache_write_(cache, x4, cos, sin, positions, index, n_heads, n_kv_heads, mode):
+    """Graph decode prologue on a packed qkv buffer x4 [B, T, H + 2 Hkv, hd]: RoPE on the q heads in
+    place and on the k heads, k / v rows into ``cache`` (bf16 pair or :class:`KV8`) at row
+    ``*index + t``, one launch, every position read on the device."""
+    if isinstance(cache, KV8):
+        _ext.ops().rope_kv_write_q8_(x4, cos, sin, positions, index, cache.kq, cache.ks, cache.vq, cache.vs,
+                                     n_heads, n_kv_heads, mode)
+    else:
+        kc, vc = cache
+        _ext.ops().rope_kv_write_(x4, cos, sin, positions, index, kc, vc, n_heads, n_kv_heads, mode)
+
+
+def _decode_q8_ok(q, cache, n):
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4 and q.shape[-1] in FLASH_HD):
+        return False
+    B, Tq, H, hd = q.shape
+    Hkv = cache.kq.shape[2]
+    if H % Hkv or Tq * (H // Hkv) > DECODE_MAX_ROWS or Tq > n:
+        return False
+    return (q.stride(3) == 1 and q.stride(0) % 4 == 0 and q.stride(1) % 4 == 0 and q.stride(2) % 4 == 0
+            and q.data_ptr() % 8 == 0)
+
+
+def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=None, fresh=None):
+    """q [B, Tq, H, hd] against rows [0, n) of ``cache`` (``n`` None: the whole buffers, with a device
+    ``kv_len``), whose last Tq rows are the query tokens.
+
+    A bf16 ``(kc, vc)`` pair: :func:`decode_attention` on the row views, as the models always did.
+    A :class:`KV8` layer: ``fresh`` = this step's bf16 (k, v) when they are the whole context (a
+    prompt prefill at position 0) is attended directly; else attn_decode_q8 over the e4m3 rows when the
+    decode kernel applies (Tq * H / Hkv <= 16, hd 64 / 128 / 256, bf16 q on the GPU); else rows [0, n)
+    are dequantised and take :func:`decode_attention`'s route (``kv_len`` cannot apply there)."""
+    if not isinstance(cache, KV8):
+        kc, vc = cache
+        if n is not None:
+            kc, vc = kc[:, :n], vc[:, :n]
+        return decode_attention(q, kc, vc, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len)
+    if fresh is not None:
+        return decode_attention(q, fresh[0], fresh[1], causal=causal, scale=scale, nsplit=nsplit)
+    rows = cache.max_len if n is None else n
+    if _decode_q8_ok(q, cache, rows):
+        sc = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        return _ext.ops().attn_decode_q8(q, cache.kq[:, :rows], cache.ks[:, :, :rows], cache.vq[:, :rows],
+                                         cache.vs[:, :, :rows], sc, causal, int(nsplit), kv_len)[0]
+    if kv_len is not None:
+        raise ValueError("kv_cache_attend: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
+    k, v = cache.dequantized(rows)
+    return decode_attention(q, k, v, causal=causal, scale=scale, nsplit=nsplit)
+
+
 def mla_decode_attention(q_abs, q_rope, cc, cr, scale, kv_len=0, kv_len_t=None, nsplit=0):
     """DeepSeek MLA decode in latent space (csrc/kernels/mla_decode.hip): q_abs [B,T,H,C]
     (q_nope with W_uk absorbed), q_rope [B,T,H,R]; caches cc [B,Smax,C], cr [B,Smax,R] with

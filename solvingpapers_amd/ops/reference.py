@@ -214,6 +214,31 @@ def grouped_gemv_w8(x, wq, s, offsets):
     return out
 
 
+def quant_kv8(x):
+    """fp8 KV-cache rows: x [B, T, Hkv, hd] -> (q float8_e4m3fn [B, T, Hkv, hd], s uint8 E8M0
+    [B, Hkv, T]) with x ~= q * 2^(s - 127), one scale per (batch, kv head, token) over the row's hd
+    values: the smallest exponent with amax / 2^e <= 448 (ops/moe.py _e8m0), the scaled values clamped
+    to +-448 and rounded to e4m3. Bit-exact with kv_quant_write_ / rope_kv_write_q8_ (csrc/kernels/rope.hip)."""
+    from .moe import _e8m0
+    xf = x.float()
+    e = _e8m0(xf.abs().amax(-1))                                            # [B, T, Hkv]
+    q = (xf * torch.exp2(-e.float())[..., None]).clamp(-448, 448).to(torch.float8_e4m3fn)
+    return q, (e + 127).to(torch.uint8).transpose(1, 2).contiguous()
+
+
+def dequant_kv8(q, s, dtype=torch.float32):
+    """Inverse of :func:`quant_kv8`: q [B, T, Hkv, hd] e4m3, s [B, Hkv, >= T] -> q * 2^(s - 127) in
+    ``dtype``. Every value is exact in bf16 and fp32."""
+    T = q.shape[1]
+    return (q.float() * torch.exp2(s[:, :, :T].float() - 127).transpose(1, 2)[..., None]).to(dtype)
+
+
+def attn_decode_q8(q, kq, ks, vq, vs, causal=True, scale=None):
+    """Decode attention over an fp8 cache (csrc/kernels/decode.hip attn_decode_q8): :func:`attention`
+    on the dequantised rows. Returns (out, lse)."""
+    return attention(_f(q), dequant_kv8(kq, ks), dequant_kv8(vq, vs), causal, scale)
+
+
 def sample_probs(logits, temperature=1.0, top_k=None, top_p=None):
     """Unnormalised fp64 sampling weights [B, V] in vocabulary order (0 for dropped tokens): the
     distribution csrc/kernels/sample.hip draws from. Order: raw logit descending, ties by ascending

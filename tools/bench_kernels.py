@@ -6,6 +6,8 @@ usage: python tools/bench_kernels.py [--iters N] [--only name,name]
 ``--only gemv`` runs just the decode GEMV rows: the fp8 weight-only kernel (gemv_w8) against the bf16
 kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only sample`` runs just the
 token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
+``--only decode_attn`` runs just the decode-attention rows: attn_decode_q8 over an fp8 KV cache against
+attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes.
 """
 import argparse
 import json
@@ -169,6 +171,45 @@ def sample_rows(iters, rounds=3):
                               "max_ms": {a: round(max(v), 5) for a, v in ms.items()}}), flush=True)
 
 
+# (H, Hkv, hd, B, Tk): LLaMA3-8B GQA at short / long caches and small / large batch, Gemma-7B MQA
+DECODE_ATTN_SHAPES = [(32, 8, 128, 1, 1024), (32, 8, 128, 1, 8192), (32, 8, 128, 16, 1024), (32, 8, 128, 16, 8192),
+                      (16, 1, 256, 16, 8192)]
+
+
+def decode_attn_rows(iters, rounds=3):
+    """attn_decode_q8 (fp8 cache) next to attn_decode (bf16 cache), one new token per sequence, same
+    process, arms alternated A B B A per round, medians. Every call reads another cache out of a ring
+    larger than the 256 MB last-level cache (the fp8 ring too), as a decode step does, where each layer's
+    cache is read once per token; one pass over the ring is one HIP-graph replay. Reported: GB/s of K/V
+    bytes (fp8: data + scale bytes) and the fp8 / bf16 time ratio (< 1: the fp8 kernel is faster)."""
+    from solvingpapers_amd.ops import reference as R
+    ops = _ext.ops()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for H, Hkv, hd, B, Tk in DECODE_ATTN_SHAPES:
+        f8_bytes = 2 * B * Tk * Hkv * (hd + 1)
+        ring = max(4, -(-(320 << 20) // f8_bytes))           # >= 320 MB of fp8 caches, twice that of bf16
+        q = torch.randn(B, 1, H, hd, device=DEV, dtype=BF, generator=g)
+        k, v = (torch.randn(B, Tk, Hkv, hd, device=DEV, dtype=BF, generator=g) for _ in range(2))
+        (kq, ks), (vq, vs) = R.quant_kv8(k), R.quant_kv8(v)
+        cb = [(k.clone(), v.clone()) for _ in range(ring)]
+        cf = [tuple(t.clone() for t in (kq, ks, vq, vs)) for _ in range(ring)]
+        sc = hd ** -0.5
+        arms = {"bf16": _graphed(lambda: [ops.attn_decode(q, ki, vi, sc, True, 0) for ki, vi in cb]),
+                "fp8": _graphed(lambda: [ops.attn_decode_q8(q, *c, sc, True, 0) for c in cf])}
+        ms = {"bf16": [], "fp8": []}
+        for _ in range(rounds):
+            for arm in ("bf16", "fp8", "fp8", "bf16"):
+                ms[arm].append(timed(arms[arm], iters) / ring)
+        mb, mf = (sorted(ms[a])[len(ms[a]) // 2] for a in ("bf16", "fp8"))
+        for arm, key, m_, nbytes in (("attn_decode", "bf16", mb, 2 * B * Tk * Hkv * hd * 2),
+                                     ("attn_decode_q8", "fp8", mf, f8_bytes)):
+            print(json.dumps({"kernel": f"{arm}_B{B}_Tk{Tk}_H{H}kv{Hkv}_hd{hd}", "ms": round(m_, 5),
+                              "GB": round(nbytes / 1e9, 4), "kv_GB_per_s": round(nbytes / m_ / 1e6, 1),
+                              "min_ms": round(min(ms[key]), 5), "max_ms": round(max(ms[key]), 5), "ring": ring,
+                              **({"time_vs_bf16": round(mf / mb, 3)} if key == "fp8" else {})}), flush=True)
+        del cb, cf, arms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -180,7 +221,9 @@ def main():
         gemv_rows(a.iters)
     if not only or "sample" in only:
         sample_rows(a.iters)
-    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample"} else cases()).items():
+    if not only or "decode_attn" in only:
+        decode_attn_rows(a.iters)
+    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn"} else cases()).items():
         if only and name not in only:
             continue
         ms = timed(fn, a.iters)
