@@ -8,7 +8,9 @@ block-scaled e4m3 images of infer.quantize_decode_weights (prefill stays on bf16
 decodes with attn_decode_q8 -- the cache's size is reported as ``kv_cache_bytes`` either way. The
 ``--sampler`` picks how the next token is drawn: ``greedy`` (argmax, captured with
 ``--graph``), ``eager`` (infer.sample(): topk / sort / softmax / multinomial launches between the replays) or ``fused``
-(infer.Sampler: one kernel, captured in the graph). The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
+(infer.Sampler: one kernel, captured in the graph). ``--prompt-lens a,b,c,...`` decodes a ragged batch (one
+prompt length per sequence, right-padded; per-sequence positions: GraphDecoder(ragged=True) with ``--graph``) and
+adds ``prompt_lens`` to the result line. The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
 from __future__ import annotations
 
 import argparse
@@ -65,9 +67,16 @@ def main(argv=None):
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--prompt-lens", default=None,
+                    help="a,b,c,...: one prompt length per sequence (ragged batch, right-padded to the longest; "
+                         "sets --batch and --prompt); with --graph the step is captured over per-sequence positions")
     a = ap.parse_args(argv)
+    lens = None
+    if a.prompt_lens is not None:
+        lens = [int(x) for x in a.prompt_lens.split(",")]
+        a.batch, a.prompt = len(lens), max(lens)
     m = build(a.model, a.layers, a.set).eval()
-    extra = {}
+    extra = {} if lens is None else {"prompt_lens": lens}
     if a.weights == "fp8":
         from solvingpapers_amd.infer import quantize_decode_weights
         rep = quantize_decode_weights(m)
@@ -82,24 +91,27 @@ def main(argv=None):
     # eager: today's sample() path with the same parameters, drawing from a seeded device generator
     kw = {} if a.sampler != "eager" else {"temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
                                           "generator": torch.Generator(device="cuda").manual_seed(a.seed)}
+    rkw = {} if lens is None else {"prompt_lens": lens}    # {}: every call as before the option existed
+    wkw = {} if lens is None else {"prompt_lens": [min(n, 64) for n in lens]}
     if a.sampler != "greedy":
         extra.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)
     if a.graph:
         from solvingpapers_amd.infer import GraphDecoder
-        dec = GraphDecoder(m, a.batch, a.prompt + a.new, greedy=a.sampler == "greedy", sampler=sampler, **ckw)
+        dec = GraphDecoder(m, a.batch, a.prompt + a.new, greedy=a.sampler == "greedy", sampler=sampler, **ckw,
+                           **({} if lens is None else {"ragged": True}))
         cache_bytes = dec.cache.nbytes() if hasattr(dec.cache, "nbytes") else None
-        dec.generate(ids[:, :64], 4, **kw)  # warm-up of the eager prefill path
+        dec.generate(ids[:, :64], 4, **kw, **wkw)  # warm-up of the eager prefill path
         if sampler is not None:
             sampler.reseed(a.seed)
-        out = dec.generate(ids, a.new, stats=st, **kw)
+        out = dec.generate(ids, a.new, stats=st, **kw, **rkw)
     else:
         kw = dict(kw, greedy=a.sampler == "greedy", sampler=sampler, **ckw)
         row = m.new_cache(a.batch, 1, **ckw)     # generate() allocates prompt + new rows of this size
         cache_bytes = row.nbytes() * (a.prompt + a.new) if hasattr(row, "nbytes") else None
-        m.generate(ids[:, :64], 4, **kw)  # warm-up (kernels, allocator)
+        m.generate(ids[:, :64], 4, **kw, **wkw)  # warm-up (kernels, allocator)
         if sampler is not None:
             sampler.reseed(a.seed)
-        out = m.generate(ids, a.new, stats=st, **kw)
+        out = m.generate(ids, a.new, stats=st, **kw, **rkw)
     torch.cuda.synchronize()
     print(json.dumps({"metric": "decode tokens/s", "model": a.model, "graph": a.graph, "batch": a.batch, "prompt": a.prompt,
                       "new_tokens": st.new_tokens, "prefill_tok_s": round(st.prefill_tok_s, 1),

@@ -34,6 +34,7 @@ struct DecodeParams {
   float* opart; float* mpart; float* lpart;  // [nsplit][B][Tq][H][hd], [nsplit][B][Tq][H]
   bf16* out; float* lse;
   const int* kv_len;  // optional device-side cache length (HIP-graph replay); else Tk
+  bool per_row;       // kv_len holds B lengths, one per sequence (ragged batch); else one for all
   int* arrivals;      // [B * Hkv] split-arrival counters (zero between launches)
   int B, Tq, Tk, H, Hkv, nsplit, chunk;
   long sqb, sqt, sqh, skb, skt, skh, svb, svt, svh, sob, sot, soh;
@@ -58,7 +59,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecodeParams p) {
   const int hk = bh % p.Hkv, b = bh / p.Hkv;
   const int G = p.H / p.Hkv;
   const int rows = G * p.Tq;
-  const int Tk = p.kv_len ? min(*p.kv_len, p.Tk) : p.Tk;
+  // valid cache rows of this block's sequence: one scalar load per block (b is block-uniform); a
+  // split that starts at or past them runs no load batch and writes the empty partial (-inf, 0)
+  const int Tk = p.kv_len ? min(p.kv_len[p.per_row ? b : 0], p.Tk) : p.Tk;
   const int k0 = split * p.chunk, k1 = min(Tk, k0 + p.chunk);
 
   // query slices (pre-scaled to log2 units), rows r = t * G + g  (head hk*G + g, token t)
@@ -292,10 +295,12 @@ static int* arrival_counters(const at::Tensor& like, hipStream_t st, int n) {
 
 // q [B, Tq, H, hd] (Tq * H / Hkv <= 16), k/v [B, Tk, Hkv, hd] strided (cache views); with
 // kv_len (device int32) k/v are the full cache buffers and only rows [0, *kv_len) count, so a
-// decode step can be captured once in a hipGraph and replayed at every position.
+// decode step can be captured once in a hipGraph and replayed at every position. per_row: kv_len is
+// [B], sequence b counts rows [0, kv_len[b]) and its query token t sits at row kv_len[b] - Tq + t.
 // Returns (out [B, Tq, H, hd] bf16, lse [B, H, Tq] fp32).
 std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
-                                    bool causal, int64_t nsplit_req, const c10::optional<at::Tensor>& kv_len) {
+                                    bool causal, int64_t nsplit_req, const c10::optional<at::Tensor>& kv_len,
+                                    bool per_row) {
   for (auto* t : {&q, &k, &v}) {
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->dim() == 4, "attn_decode: bf16 [B,T,H,hd]");
     TORCH_CHECK(t->stride(3) == 1 && t->stride(2) % 4 == 0 && t->stride(1) % 4 == 0 && t->stride(0) % 4 == 0 &&
@@ -343,7 +348,12 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k, co
   if (kv_len.has_value()) {  // k/v are the whole cache; the valid length lives on the device
     TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
                 "attn_decode: kv_len must be a device int32 tensor");
+    TORCH_CHECK(!per_row || (kv_len->numel() == B && kv_len->is_contiguous()),
+                "attn_decode: per_row needs one kv_len per sequence (", B, "), got ", kv_len->numel());
     p.kv_len = kv_len->data_ptr<int>();
+    p.per_row = per_row;
+  } else {
+    TORCH_CHECK(!per_row, "attn_decode: per_row needs a device int32 kv_len [B]");
   }
   auto st = stream();
   const char* env = getenv("SPA_DECODE_FUSED");
@@ -440,7 +450,9 @@ __global__ __launch_bounds__(256) void attn_decode_q8_kernel(DecodeQ8Params pp) 
   const int hk = bh % p.Hkv, b = bh / p.Hkv;
   const int G = p.H / p.Hkv;
   const int rows = G * p.Tq;
-  const int Tk = p.kv_len ? min(*p.kv_len, p.Tk) : p.Tk;
+  // valid cache rows of this block's sequence: one scalar load per block (b is block-uniform); a
+  // split that starts at or past them runs no load batch and writes the empty partial (-inf, 0)
+  const int Tk = p.kv_len ? min(p.kv_len[p.per_row ? b : 0], p.Tk) : p.Tk;
   const int k0 = split * p.chunk, k1 = min(Tk, k0 + p.chunk);
 
   // query slices (pre-scaled to log2 units, fp32), rows r = t * G + g  (head hk*G + g, token t)
@@ -579,7 +591,7 @@ __global__ __launch_bounds__(256) void attn_decode_q8_kernel(DecodeQ8Params pp) 
 // Same contract and return as attn_decode.
 std::vector<at::Tensor> attn_decode_q8(const at::Tensor& q, const at::Tensor& kq, const at::Tensor& ks,
                                        const at::Tensor& vq, const at::Tensor& vs, double scale, bool causal,
-                                       int64_t nsplit_req, const c10::optional<at::Tensor>& kv_len) {
+                                       int64_t nsplit_req, const c10::optional<at::Tensor>& kv_len, bool per_row) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.dim() == 4, "attn_decode_q8: q must be bf16 [B,T,H,hd]");
   TORCH_CHECK(q.stride(3) == 1 && q.stride(2) % 4 == 0 && q.stride(1) % 4 == 0 && q.stride(0) % 4 == 0 &&
                   ((uintptr_t)q.data_ptr() % 8) == 0,
@@ -643,7 +655,12 @@ std::vector<at::Tensor> attn_decode_q8(const at::Tensor& q, const at::Tensor& kq
   if (kv_len.has_value()) {  // the whole cache; the valid length lives on the device
     TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
                 "attn_decode_q8: kv_len must be a device int32 tensor");
+    TORCH_CHECK(!per_row || (kv_len->numel() == B && kv_len->is_contiguous()),
+                "attn_decode_q8: per_row needs one kv_len per sequence (", B, "), got ", kv_len->numel());
     p.kv_len = kv_len->data_ptr<int>();
+    p.per_row = per_row;
+  } else {
+    TORCH_CHECK(!per_row, "attn_decode_q8: per_row needs a device int32 kv_len [B]");
   }
   auto st = stream();
   const dim3 grid(B * Hkv, nsplit);
@@ -666,9 +683,10 @@ std::vector<at::Tensor> attn_decode_q8(const at::Tensor& q, const at::Tensor& kq
 }  // namespace spa
 
 TORCH_LIBRARY_FRAGMENT(spa, m) {
-  m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, bool causal, int nsplit, Tensor? kv_len=None) -> Tensor[]");
+  m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, bool causal, int nsplit, Tensor? kv_len=None, "
+        "bool per_row=False) -> Tensor[]");
   m.def("attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, float scale, bool causal, int nsplit, "
-        "Tensor? kv_len=None) -> Tensor[]");
+        "Tensor? kv_len=None, bool per_row=False) -> Tensor[]");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("attn_decode", &spa::attn_decode);

@@ -9,6 +9,8 @@
 // column gathers on distinct banks) -> 8 column elements per thread -> 16-byte global stores.
 #include "spa_common.h"
 
+SPA_DEBUG_TU("layout.hip")
+
 namespace spa {
 
 // build-time A/B knobs (profiles/r5_transpose_variants.txt): tile size, diagonal block order
@@ -111,13 +113,57 @@ void stream_copy_wg(const at::Tensor& src, at::Tensor& dst, int64_t nwg, int64_t
   SPA_LAUNCH_CHECK();
 }
 
+// Row gather for ragged batches: out[b, 0, :] = x[b, idx[b], :], the last real prompt position of each
+// right-padded sequence, taken before the LM head so the head runs on B rows instead of B * T. idx is
+// read on the device (no host sync: graph-safe); rows move as 16-byte units, one per thread. An idx
+// outside [0, T) is clamped (the debug build records it).
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ x, const int64_t* __restrict__ idx,
+                                                          uint4* __restrict__ out, int B, int T, int nv, long sb,
+                                                          long st) {
+  const long total = (long)B * nv;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int v = i % nv, b = i / nv;
+    const long t = idx[b];
+    SPA_DBG_CHECK(t, T);
+    const long tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
+    out[i] = x[b * sb + tc * st + v];
+  }
+}
+
+// x [B, T, D] (D contiguous, 16-byte rows), idx int64 [B] -> [B, 1, D]
+at::Tensor gather_rows(const at::Tensor& x, const at::Tensor& idx) {
+  SPA_CHECK_CUDA(x);
+  TORCH_CHECK(x.dim() == 3 && x.stride(2) == 1, "gather_rows: x must be [B, T, D] with contiguous D");
+  const int B = x.size(0), T = x.size(1);
+  const long D = x.size(2), es = x.element_size();
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong && idx.numel() == B && idx.is_contiguous(),
+              "gather_rows: idx must be a device int64 tensor of ", B, " elements");
+  TORCH_CHECK(T > 0 || B == 0, "gather_rows: no rows to pick from");
+  TORCH_CHECK((D * es) % 16 == 0 && (x.stride(0) * es) % 16 == 0 && (x.stride(1) * es) % 16 == 0 &&
+                  (uintptr_t)x.data_ptr() % 16 == 0,
+              "gather_rows: rows must be 16-byte multiples, 16-byte aligned");
+  DeviceGuard g(x.device());
+  auto out = at::empty({B, 1, D}, x.options());
+  const int nv = (int)(D * es / 16);
+  const long total = (long)B * nv;
+  if (total == 0) return out;
+  const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  gather_rows_kernel<<<grid, 256, 0, stream()>>>((const uint4*)x.data_ptr(), idx.data_ptr<int64_t>(),
+                                                 (uint4*)out.data_ptr(), B, T, nv, x.stride(0) * es / 16,
+                                                 x.stride(1) * es / 16);
+  SPA_LAUNCH_CHECK();
+  return out;
+}
+
 }  // namespace spa
 
 TORCH_LIBRARY_FRAGMENT(spa, m) {
   m.def("transpose2d(Tensor x) -> Tensor");
+  m.def("gather_rows(Tensor x, Tensor idx) -> Tensor");
   m.def("stream_copy_wg(Tensor src, Tensor(a!) dst, int nwg, int reps) -> ()");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("transpose2d", &spa::transpose2d);
+  m.impl("gather_rows", &spa::gather_rows);
   m.impl("stream_copy_wg", &spa::stream_copy_wg);
 }

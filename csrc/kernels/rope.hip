@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(bf16* __restrict__ x
                                                             bf16* __restrict__ vc, long sb, long st, long sh,
                                                             long kcb, long kct, long kch, long vcb, long vct,
                                                             long vch, int B, int T, int H, int Hkv, int hd,
-                                                            int Tmax) {
+                                                            int Tmax, bool per_row) {
   const int vpr = hd / 8;
   const int NH = H + 2 * Hkv;
   const long total = (long)B * T * NH * vpr;
@@ -147,8 +147,10 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(bf16* __restrict__ x
     r /= NH;
     const int t = r % T;
     const int b = r / T;
-    const long row = row0 + t;
-    if (hh >= H && row >= Tmax) continue;
+    SPA_DBG_CHECK(b, B);  // the per-row index read (debug build)
+    const long row = (per_row ? index[b] : row0) + t;  // ragged batch: each sequence's own cache row
+    if (hh >= H && (row >= Tmax || row < 0)) continue;
+    if (hh >= H && !SPA_DBG_OK(row, Tmax)) continue;
     const bf16* src = x + b * sb + t * st + hh * sh;
     bf16* dst = hh < H ? x + b * sb + t * st + hh * sh
                        : (hh < H + Hkv ? kc + b * kcb + row * kct + (hh - H) * kch
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(bf16* __restrict__ x
 
 void rope_kv_write_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
                     const at::Tensor& index, const at::Tensor& kc, const at::Tensor& vc, int64_t H, int64_t Hkv,
-                    int64_t mode) {
+                    int64_t mode, bool per_row) {
   for (auto* t : {&x, &kc, &vc}) {
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->dim() == 4 && t->stride(3) == 1,
                 "rope_kv_write: bf16 [B, T, heads, hd] tensors with contiguous hd");
@@ -213,6 +215,8 @@ void rope_kv_write_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor
               "rope_kv_write: pos must be device int32 [B, T]");
   TORCH_CHECK(index.is_cuda() && index.scalar_type() == at::kLong && index.numel() >= 1,
               "rope_kv_write: index must be a device int64 tensor");
+  TORCH_CHECK(!per_row || (index.numel() == B && index.is_contiguous()),
+              "rope_kv_write: per_row needs one index per sequence (", B, "), got ", index.numel());
   TORCH_CHECK(mode == 0 || mode == 1, "rope_kv_write: mode 0 (interleaved) or 1 (rotate_half)");
   DeviceGuard g(x.device());
   const long total = (long)B * T * (H + 2 * Hkv) * (hd / 8);
@@ -224,7 +228,7 @@ void rope_kv_write_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor
         (bf16*)x.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(),
         index.data_ptr<int64_t>(), (bf16*)kc.data_ptr(), (bf16*)vc.data_ptr(), x.stride(0), x.stride(1),
         x.stride(2), kc.stride(0), kc.stride(1), kc.stride(2), vc.stride(0), vc.stride(1), vc.stride(2), B, T,
-        (int)H, (int)Hkv, hd, (int)kc.size(1));
+        (int)H, (int)Hkv, hd, (int)kc.size(1), per_row);
   };
   if (mode == 0) launch(std::integral_constant<int, 0>{});
   else launch(std::integral_constant<int, 1>{});
@@ -328,7 +332,7 @@ __global__ __launch_bounds__(256) void rope_kv_write_q8_kernel(bf16* __restrict_
                                                                const int* __restrict__ pos,
                                                                const long* __restrict__ index, KV8Dst kd, KV8Dst vd,
                                                                long sb, long st, long sh, int B, int T, int H, int Hkv,
-                                                               int hd, int Tmax) {
+                                                               int hd, int Tmax, bool per_row) {
   const int vpr = hd / 8;
   const int NH = H + 2 * Hkv;
   const long total = (long)B * T * NH * vpr;
@@ -340,7 +344,8 @@ __global__ __launch_bounds__(256) void rope_kv_write_q8_kernel(bf16* __restrict_
     r /= NH;
     const int t = r % T;
     const int b = r / T;
-    const long row = row0 + t;
+    SPA_DBG_CHECK(b, B);  // the per-row index read (debug build)
+    const long row = (per_row ? index[b] : row0) + t;  // ragged batch: each sequence's own cache row
     if (hh >= H && (row >= Tmax || row < 0)) continue;  // whole lane groups: hh and row are uniform in a row
     bf16* src = x + b * sb + t * st + hh * sh;
     float a[8], bq[8];
@@ -410,7 +415,7 @@ __global__ __launch_bounds__(256) void rope_kv_write_q8_kernel(bf16* __restrict_
 
 void rope_kv_write_q8_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
                        const at::Tensor& index, const at::Tensor& kq, const at::Tensor& ks, const at::Tensor& vq,
-                       const at::Tensor& vs, int64_t H, int64_t Hkv, int64_t mode) {
+                       const at::Tensor& vs, int64_t H, int64_t Hkv, int64_t mode, bool per_row) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 && x.stride(3) == 1,
               "rope_kv_write_q8: bf16 [B, T, heads, hd] qkv with contiguous hd");
   TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(1) % 8 == 0 && x.stride(2) % 8 == 0 && (uintptr_t)x.data_ptr() % 16 == 0,
@@ -426,6 +431,8 @@ void rope_kv_write_q8_(const at::Tensor& x, const at::Tensor& cos, const at::Ten
               "rope_kv_write_q8: pos must be device int32 [B, T]");
   TORCH_CHECK(index.is_cuda() && index.scalar_type() == at::kLong && index.numel() >= 1,
               "rope_kv_write_q8: index must be a device int64 tensor");
+  TORCH_CHECK(!per_row || (index.numel() == B && index.is_contiguous()),
+              "rope_kv_write_q8: per_row needs one index per sequence (", B, "), got ", index.numel());
   TORCH_CHECK(mode == 0 || mode == 1, "rope_kv_write_q8: mode 0 (interleaved) or 1 (rotate_half)");
   DeviceGuard g(x.device());
   const long total = (long)B * T * (H + 2 * Hkv) * (hd / 8);
@@ -436,7 +443,7 @@ void rope_kv_write_q8_(const at::Tensor& x, const at::Tensor& cos, const at::Ten
     rope_kv_write_q8_kernel<M><<<grid, 256, 0, stream()>>>(
         (bf16*)x.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(),
         index.data_ptr<int64_t>(), kd, vd, x.stride(0), x.stride(1), x.stride(2), B, T, (int)H, (int)Hkv, hd,
-        (int)kq.size(1));
+        (int)kq.size(1), per_row);
   };
   if (mode == 0) launch(std::integral_constant<int, 0>{});
   else launch(std::integral_constant<int, 1>{});
@@ -449,10 +456,11 @@ TORCH_LIBRARY_FRAGMENT(spa, m) {
   m.def("rope_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor? pos, int nrot, int pos_off, int mode, "
         "bool inverse) -> ()");
   m.def("rope_kv_write_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kc, "
-        "Tensor(c!) vc, int n_heads, int n_kv_heads, int mode=0) -> ()");
+        "Tensor(c!) vc, int n_heads, int n_kv_heads, int mode=0, bool per_row=False) -> ()");
   m.def("kv_quant_write_(Tensor k, Tensor v, Tensor(a!) kq, Tensor(b!) ks, Tensor(c!) vq, Tensor(d!) vs, int pos) -> ()");
   m.def("rope_kv_write_q8_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kq, "
-        "Tensor(c!) ks, Tensor(d!) vq, Tensor(e!) vs, int n_heads, int n_kv_heads, int mode=0) -> ()");
+        "Tensor(c!) ks, Tensor(d!) vq, Tensor(e!) vs, int n_heads, int n_kv_heads, int mode=0, "
+        "bool per_row=False) -> ()");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("rope_", &spa::rope_);

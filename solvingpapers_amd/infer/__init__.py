@@ -8,7 +8,8 @@
   E8M0 scales, one :class:`KV8` handle per layer, read by the fp8 decode-attention kernel;
 * :func:`generate` -- prompt prefill (flash attention) + token-by-token decode (split-K
   decode kernel, csrc/kernels/decode.hip) with the model's own cache layout, timing
-  prefill and decode separately;
+  prefill and decode separately; ``prompt_lens=`` takes a right-padded batch of prompts of different
+  lengths (ragged batch: per-sequence positions in :class:`RaggedDecodeState`; LLaMA3 and Gemma);
 * :func:`quantize_decode_weights` / :func:`clear_decode_weights` -- fp8 weight-only decode:
   block-scaled e4m3 images of the projection matrices, read by the decode GEMV kernels
   (csrc/kernels/gemv.hip); see infer/quant.py.
@@ -20,9 +21,9 @@ deepseekv3/deepseekv3.ipynb:1849-1873.
 from ..ops.attention import KV8
 from .cache import KV_CACHE_FORMATS, KVCache
 from .generate import GenerationStats, generate
-from .graph import DecodeState, GraphDecoder
+from .graph import DecodeState, GraphDecoder, RaggedDecodeState
 from .quant import clear_decode_weights, quantize_decode_weights
 from .sampling import Sampler, sample
 
-__all__ = ["KV8", "KV_CACHE_FORMATS", "KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "Sampler", "clear_decode_weights", "generate",
-           "quantize_decode_weights", "sample"]
+__all__ = ["KV8", "KV_CACHE_FORMATS", "KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "RaggedDecodeState",
+           "Sampler", "clear_decode_weights", "generate", "quantize_decode_weights", "sample"]

@@ -74,6 +74,20 @@ class KVCache(list):
         kc, vc = self[layer]
         return kc[:, :n], vc[:, :n]
 
+    def rows(self, b0: int, b1: int) -> "KVCache":
+        """A cache of views of batch rows [b0, b1) (per layer the ``(k, v)`` slices, or a KV8 of the
+        data and scale slices): what ``model.step`` writes through it lands in this cache, so one slot
+        of a running batch can be prefilled alone."""
+        if not 0 <= b0 < b1 <= (self[0].kq if self.quant else self[0][0]).shape[0]:
+            raise IndexError(f"KVCache.rows: [{b0}, {b1}) outside the batch")
+        sub = KVCache.__new__(KVCache)
+        if self.quant:
+            list.__init__(sub, (KV8(l.kq[b0:b1], l.ks[b0:b1], l.vq[b0:b1], l.vs[b0:b1], l.dtype) for l in self))
+        else:
+            list.__init__(sub, ((k[b0:b1], v[b0:b1]) for k, v in self))
+        sub.max_len, sub.pos, sub.quant = self.max_len, self.pos, self.quant
+        return sub
+
     def nbytes(self) -> int:
         if self.quant:
             return sum(l.nbytes() for l in self)

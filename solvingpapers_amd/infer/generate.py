@@ -5,6 +5,8 @@ Protocol a model implements for cached decoding:
   ``step(ids, cache, pos)``      -> logits [B, V] of the LAST position of ``ids``, after
                                     writing ``ids``' keys/values at cache rows [pos, pos+T)
   ``max_context`` (attribute, optional) -> the longest sequence the model accepts
+  ragged batches (``prompt_lens=``) also need ``step(..., last=)`` (logits at row last[b] of each
+  sequence), ``step_graph(ids, cache, state)`` and the class attribute ``ragged_decode = True``
 
 The first call is the prompt prefill (flash attention over the whole prompt), every later
 call feeds one token per sequence (split-K decode attention). Models without the protocol
@@ -46,18 +48,80 @@ def _sync(t: torch.Tensor):
         torch.cuda.synchronize(t.device)
 
 
+def _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temperature, top_k, top_p, greedy,
+                     eos_token_id, generator, st, timed, sampler, kv_cache):
+    """Ragged batch: one right-padded prefill whose logits are gathered at each sequence's last real
+    token (causal attention keeps real tokens independent of the pads to their right), then
+    ``step_graph`` run eagerly on a RaggedDecodeState positioned at ``prompt_lens``: sequence b writes
+    cache row len_b + i at step i (over the pad rows the prefill left there) and attends over its own
+    kv_len[b] rows."""
+    from .graph import RAGGED_UNSUPPORTED, RaggedDecodeState, check_prompt_lens, ragged_layout
+    if not getattr(model, "ragged_decode", False):
+        raise NotImplementedError(RAGGED_UNSUPPORTED.format(type(model).__name__))
+    B, T0 = ids.shape
+    lens = check_prompt_lens(prompt_lens, B, T0, ids.device)
+    longest = int(lens.max())
+    total = T0 + max_new_tokens
+    limit = getattr(model, "max_context", None)
+    if limit is not None:
+        if T0 > limit:
+            raise ValueError(f"padded prompts of {T0} tokens exceed the model's context of {limit}")
+        total = min(total, limit)
+    st.cached = True
+    cache = model.new_cache(B, total) if kv_cache is None else model.new_cache(B, total, kv_cache=kv_cache)
+    if timed:
+        _sync(ids)
+    t0 = time.perf_counter()
+    logits = model.step(ids, cache, 0, last=lens - 1)
+    state = RaggedDecodeState(B, total, ids.device)
+    state.set(lens)
+    if timed:
+        _sync(ids)
+    t1 = time.perf_counter()
+    st.prompt_tokens += int(lens.sum())
+    st.prefill_s += t1 - t0
+    done = torch.zeros(B, dtype=torch.bool, device=ids.device)
+    new = []
+    while len(new) < max_new_tokens:
+        nxt = sampler(logits) if sampler is not None else sample(logits, temperature, top_k, greedy, generator, top_p)
+        if eos_token_id is not None:
+            nxt = torch.where(done[:, None], torch.full_like(nxt, pad_token_id), nxt)   # a finished row pads
+            done |= nxt[:, 0] == eos_token_id
+            state.active.copy_(~done)   # ... and stays at its position: its steps touch its own row only
+        new.append(nxt)
+        n = len(new)
+        # the next step feeds token n - 1 of every row at cache row len_b + n - 1
+        if n >= max_new_tokens or longest + n - 1 >= total:
+            break
+        if eos_token_id is not None and n % 16 == 0 and bool(done.all()):
+            break
+        logits = model.step_graph(nxt, cache, state)
+        state.advance()
+    if timed:
+        _sync(ids)
+    st.decode_s += time.perf_counter() - t1
+    st.new_tokens += B * len(new)
+    return ragged_layout(ids, lens, torch.cat(new, 1) if new else ids.new_zeros(B, 0), pad_token_id)
+
+
 @torch.no_grad()
 def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
              top_k: Optional[int] = None, top_p: Optional[float] = None, greedy: bool = False,
              eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              stats: Optional[GenerationStats] = None, timed: bool = False, sampler=None,
-             kv_cache: Optional[str] = None) -> torch.Tensor:
+             kv_cache: Optional[str] = None, prompt_lens=None, pad_token_id: int = 0) -> torch.Tensor:
     """ids [B, T0] -> [B, T0 + n] (n <= max_new_tokens; stops early once every sequence has
     produced ``eos_token_id``, checked every 16 tokens to keep the host out of the loop).
     ``sampler`` (an infer.Sampler) replaces ``sample(...)``: one fused launch per token on the GPU,
     the fp64 oracle on the CPU, both drawing u01(seed, call * B + row).
     ``kv_cache="fp8"`` decodes from an e4m3 KV cache (infer/cache.py; models with ``new_cache(...,
-    kv_cache=)``); None / "bf16": the model-dtype cache."""
+    kv_cache=)``); None / "bf16": the model-dtype cache.
+
+    ``prompt_lens`` (length-B tensor or list, 1 <= len_b <= T0): a ragged batch. ``ids`` is
+    RIGHT-padded (what stands after a row's len_b tokens is ignored), every sequence decodes from
+    its own position, and row b of the result holds its prompt, its n new tokens from column len_b,
+    then ``pad_token_id`` (also after a row's ``eos_token_id``). Models with ``step_graph`` and a
+    (k, v) cache: LLaMA3 and Gemma."""
     was = model.training
     model.eval()
     timed = timed or stats is not None  # stats requested -> device-synchronised phase timings
@@ -67,7 +131,10 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
     out = ids
     done = torch.zeros(B, dtype=torch.bool, device=ids.device)
     try:
-        if hasattr(model, "new_cache") and hasattr(model, "step"):
+        if prompt_lens is not None:
+            out = _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temperature, top_k, top_p,
+                                   greedy, eos_token_id, generator, st, timed, sampler, kv_cache)
+        elif hasattr(model, "new_cache") and hasattr(model, "step"):
             st.cached = True
             total = T0 + max_new_tokens
             if limit is not None:

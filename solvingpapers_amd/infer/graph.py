@@ -17,8 +17,14 @@ counter RNG, written into the same token buffer): non-greedy generation is ``n``
 Without one, non-greedy sampling runs eagerly on the replay's logits between replays
 (torch.multinomial).
 
+``GraphDecoder(ragged=True)`` captures the same step over a ``RaggedDecodeState``: the three
+tensors hold one entry per sequence (``index`` long [B], ``kv_len`` int32 [B]), the kernels read
+entry b for sequence b, so right-padded prompts of different lengths decode together and
+``prefill_row`` puts a new prompt into one slot while the others continue.
+
 Protocol a model implements: ``new_cache(B, max_len)``, ``step(ids, cache, pos)`` (eager
-prefill) and ``step_graph(ids, cache, state)`` (graph-safe decode step: no host syncs).
+prefill; ``last=`` for a ragged one) and ``step_graph(ids, cache, state)`` (graph-safe decode
+step: no host syncs).
 """
 from __future__ import annotations
 
@@ -31,6 +37,8 @@ from .sampling import sample
 
 class DecodeState:
     """Device-resident position state of a captured decode step (batch-uniform positions)."""
+
+    per_row = False   # one position for the whole batch; RaggedDecodeState: one per sequence
 
     def __init__(self, batch: int, max_len: int, device):
         self.batch, self.max_len = batch, max_len
@@ -51,16 +59,84 @@ class DecodeState:
         self.kv_len.add_(1)
 
 
+class RaggedDecodeState(DecodeState):
+    """Per-sequence positions (ragged batch: prompts of different lengths, slot reuse): ``index`` long
+    [B], ``positions`` int32 [B, 1], ``kv_len`` int32 [B]; the kernels read entry b for sequence b
+    (``per_row``). ``active`` int32 [B] (ones) is what ``advance`` adds: a row with ``active[b] = 0``
+    stays where it is and recomputes its current position at every step -- its logits are unspecified
+    (finite), it rewrites only its own cache row, and it never touches another row's cache."""
+
+    per_row = True
+
+    def __init__(self, batch: int, max_len: int, device):
+        self.batch, self.max_len = batch, max_len
+        self.index = torch.zeros(batch, dtype=torch.long, device=device)
+        self.positions = torch.zeros(batch, 1, dtype=torch.int32, device=device)
+        self.kv_len = torch.ones(batch, dtype=torch.int32, device=device)
+        self.active = torch.ones(batch, dtype=torch.int32, device=device)
+
+    def set(self, pos):
+        """Host-side (re)position of every row: an int, or one position per sequence (tensor / sequence
+        of length B). Row b's next step writes cache row ``pos[b]``."""
+        if isinstance(pos, int):
+            return super().set(pos)
+        p = torch.as_tensor(pos, device=self.index.device).reshape(-1).long()
+        if p.numel() != self.batch:
+            raise ValueError(f"RaggedDecodeState.set: {p.numel()} positions for a batch of {self.batch}")
+        self.index.copy_(p)
+        self.positions.copy_(p[:, None])
+        self.kv_len.copy_(p + 1)
+
+    def set_row(self, b: int, pos: int):
+        """(Re)position sequence ``b`` alone (a new prompt in a freed slot); the others keep theirs."""
+        self.index[b:b + 1].fill_(pos)
+        self.positions[b:b + 1].fill_(pos)
+        self.kv_len[b:b + 1].fill_(pos + 1)
+
+    def advance(self):
+        """Device-side increment of the active rows (captured at the end of the step)."""
+        self.index.add_(self.active)
+        self.positions.add_(self.active[:, None])
+        self.kv_len.add_(self.active)
+
+
+def ragged_layout(ids: torch.Tensor, lens: torch.Tensor, new: torch.Tensor, pad_token_id: int) -> torch.Tensor:
+    """[B, T0 + n]: row b = its prompt ids[b, :lens[b]], its n new tokens from column lens[b], then
+    ``pad_token_id`` (the output layout of ragged generation)."""
+    B, T0 = ids.shape
+    n = new.shape[1]
+    out = torch.full((B, T0 + n), pad_token_id, dtype=ids.dtype, device=ids.device)
+    out[:, :T0] = torch.where(torch.arange(T0, device=ids.device)[None] < lens[:, None], ids, out[:, :T0])
+    return out.scatter_(1, lens[:, None] + torch.arange(n, device=ids.device)[None], new.to(ids.dtype))
+
+
+def check_prompt_lens(prompt_lens, B: int, T0: int, device) -> torch.Tensor:
+    """``prompt_lens`` (tensor or sequence) as a long [B] tensor on ``device``, 1 <= len_b <= T0."""
+    lens = torch.as_tensor(prompt_lens).reshape(-1).long()
+    if lens.numel() != B:
+        raise ValueError(f"prompt_lens: {lens.numel()} lengths for a batch of {B}")
+    if int(lens.min()) < 1 or int(lens.max()) > T0:
+        raise ValueError(f"prompt_lens must lie in [1, {T0}] (ids are right-padded to {T0}), got {lens.tolist()}")
+    return lens.to(device)
+
+
+RAGGED_UNSUPPORTED = ("ragged batches (per-sequence positions) cover the RoPE models with a (k, v) cache, LLaMA3 and "
+                      "Gemma; {} is not covered")
+
+
 class GraphDecoder:
     def __init__(self, model, batch: int, max_len: int, greedy: bool = True, warmup: int = 2, sampler=None,
-                 kv_cache: Optional[str] = None):
+                 kv_cache: Optional[str] = None, ragged: bool = False):
+        """``ragged=True`` captures the step over a :class:`RaggedDecodeState`: every sequence at its own
+        position (prompts of different lengths, ``prefill_row`` to refill one slot mid-stream)."""
         self.model, self.batch, self.max_len, self.greedy = model, batch, max_len, greedy
+        self.ragged = ragged
         dev = next(model.parameters()).device
         self.sampler = sampler.to(dev) if sampler is not None else None
         # kv_cache="fp8": the captured step quantises its K/V row and attends over e4m3 rows
         self.cache = model.new_cache(batch, max_len) if kv_cache is None else \
             model.new_cache(batch, max_len, kv_cache=kv_cache)
-        self.state = DecodeState(batch, max_len, dev)
+        self.state = RaggedDecodeState(batch, max_len, dev) if ragged else DecodeState(batch, max_len, dev)
         self.ids = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.logits: Optional[torch.Tensor] = None
         self._capture(warmup)
@@ -94,19 +170,53 @@ class GraphDecoder:
             self.sampler.offset.zero_()
 
     @torch.no_grad()
-    def prefill(self, ids: torch.Tensor) -> torch.Tensor:
+    def prefill(self, ids: torch.Tensor, prompt_lens=None) -> torch.Tensor:
         """Eager prompt pass: fills cache rows [0, T0), positions the state at T0 and returns
-        the last position's logits."""
+        the last position's logits. ``prompt_lens`` (``ragged=True`` only): ``ids`` is right-padded,
+        sequence b has ``prompt_lens[b]`` real tokens; its logits are those of its last real token and
+        its state is positioned at ``prompt_lens[b]`` (the pad rows the pass wrote into the cache lie
+        beyond kv_len and are overwritten as the sequence grows)."""
         T0 = ids.shape[1]
         if T0 >= self.max_len:
             raise ValueError(f"prompt of {T0} tokens leaves no room in a {self.max_len}-token cache")
-        lg = self.model.step(ids, self.cache, 0)
-        self.state.set(T0)
+        if self.ragged:
+            self.state.active.fill_(1)   # a batch prefill restarts every slot
+        if prompt_lens is None:
+            lg = self.model.step(ids, self.cache, 0)
+            self.state.set(T0)
+            return lg
+        if not self.ragged:
+            raise ValueError("GraphDecoder: prompt_lens needs ragged=True (the uniform state holds one position)")
+        lens = check_prompt_lens(prompt_lens, self.batch, T0, ids.device)
+        lg = self.model.step(ids, self.cache, 0, last=lens - 1)
+        self.state.set(lens)
         return lg
 
     @torch.no_grad()
+    def prefill_row(self, b: int, ids: torch.Tensor) -> torch.Tensor:
+        """Prefill one sequence (``ids`` 1-D) into slot ``b`` while the other slots keep their cache
+        rows and positions (``ragged=True``): the prompt runs through the batch-row views
+        ``cache.rows(b, b + 1)`` and ``state.set_row`` positions the slot behind it. Returns the
+        prompt's last-position logits [V]; feeding the next token (``self.ids[b]``) and
+        ``state.active[b]`` are the caller's."""
+        if not self.ragged:
+            raise ValueError("GraphDecoder: prefill_row needs ragged=True")
+        if not 0 <= b < self.batch:
+            raise IndexError(f"slot {b} of {self.batch}")
+        ids = ids.reshape(1, -1)
+        T = ids.shape[1]
+        if not 1 <= T < self.max_len:
+            raise ValueError(f"prompt of {T} tokens does not fit a {self.max_len}-token cache")
+        lg = self.model.step(ids, self.cache.rows(b, b + 1), 0)
+        self.state.set_row(b, T)
+        return lg[0]
+
+    @torch.no_grad()
     def generate(self, ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k=None,
-                 top_p=None, generator=None, stats=None) -> torch.Tensor:
+                 top_p=None, generator=None, stats=None, prompt_lens=None, pad_token_id: int = 0) -> torch.Tensor:
+        """``prompt_lens`` (``ragged=True``): right-padded prompts of different lengths; returns
+        [B, T0 + n] with row b = its prompt, its n new tokens from column ``prompt_lens[b]``, then
+        ``pad_token_id``."""
         import time
         if self.sampler is not None and (temperature != 1.0 or top_k is not None or top_p is not None
                                          or generator is not None):
@@ -115,11 +225,15 @@ class GraphDecoder:
         if stats is not None:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        lg = self.prefill(ids)
+        lens = None
+        if prompt_lens is not None:
+            lens = check_prompt_lens(prompt_lens, self.batch, ids.shape[1], ids.device)
+        lg = self.prefill(ids, lens)
         if stats is not None:
             torch.cuda.synchronize()
         t1 = time.perf_counter()
-        n = min(max_new_tokens, self.max_len - ids.shape[1] + 1)
+        # the i-th replay writes cache row len + i of every sequence: the longest prompt sets the room
+        n = min(max_new_tokens, self.max_len - (ids.shape[1] if lens is None else int(lens.max())) + 1)
         out = torch.empty(self.batch, n, dtype=torch.long, device=ids.device)
         if self.sampler is not None:
             self.sampler(lg, out=self.ids)   # the first token: same kernel, next offset of the stream
@@ -137,8 +251,10 @@ class GraphDecoder:
         if stats is not None:
             torch.cuda.synchronize()
             stats.cached = True
-            stats.prompt_tokens += ids.numel()
+            stats.prompt_tokens += ids.numel() if lens is None else int(lens.sum())
             stats.new_tokens += self.batch * n
             stats.prefill_s += t1 - t0
             stats.decode_s += time.perf_counter() - t1
+        if lens is not None:
+            return ragged_layout(ids, lens, out, pad_token_id)
         return torch.cat([ids, out], 1)

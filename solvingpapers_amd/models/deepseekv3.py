@@ -50,6 +50,8 @@ from ..utils.grad import mark_ready
 from ..infer.sampling import sample
 
 FP32_EPS = float(torch.finfo(torch.float32).eps)
+_RAGGED = ("DeepSeek-V3: ragged batches (prompt_lens / per-sequence positions) are not covered: the MLA latent "
+           "cache and its decode kernel (mla_decode) keep one length for the whole batch; pass equal-length prompts")
 
 
 @dataclass
@@ -882,9 +884,12 @@ class DeepSeekV3(tnn.Module):
     def max_context(self):
         return self.c.block_size if self.c.pos_emb == "sinusoidal" else None
 
-    def step(self, ids, cache, pos):
+    def step(self, ids, cache, pos, last=None):
         """Write ids' latents at cache rows [pos, pos+T), return the last position's logits [B, V].
-        Always the exact EP dispatch: capacity mode's overflow re-run exists only for forward()."""
+        Always the exact EP dispatch: capacity mode's overflow re-run exists only for forward().
+        Ragged batches (``last``) are not covered."""
+        if last is not None:
+            raise NotImplementedError(_RAGGED)
         with self.ep_dispatch("exact"):
             n, _ = self.hidden(ids, cache, pos)
         return self.logits(n[:, -1:]).float()[:, -1]
@@ -896,6 +901,8 @@ class DeepSeekV3(tnn.Module):
         MoE routing / permutation / grouped GEMMs never read device values on the host."""
         if self.c.attention == "ref":
             raise NotImplementedError("graph decode needs the paper MLA (the ref preset adds sinusoidal PE by position)")
+        if getattr(state, "per_row", False):
+            raise NotImplementedError(_RAGGED)
         # EP > 1: fixed blocks at the exact per-peer bound (no host read, no overflow, no flag)
         with self.ep_dispatch("bound"):
             n, _ = self.hidden(ids, cache, state)
@@ -903,11 +910,14 @@ class DeepSeekV3(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None, prompt_lens=None,
+                 pad_token_id=0):
         """Cached decoding (ref: one latent cache, Q1; mla: per-layer compressed cache).
         Reference sampling (deepseekv3.ipynb:1850-1873) recomputes the whole prefix per token
         with top-k + temperature; results are identical, the cache removes the recompute."""
         from ..infer.generate import generate
+        if prompt_lens is not None:
+            raise NotImplementedError(_RAGGED)
         return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
                         sampler=sampler, kv_cache=kv_cache)
 

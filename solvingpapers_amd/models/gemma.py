@@ -267,8 +267,8 @@ class GemmaBlock(tnn.Module):
             cos, sin = RopeCache.get(pos.max_len, hd, c.rope_theta, qkv.device)
             # one launch: rotate_half RoPE on q (in place) and k, k/v rows into the cache (an fp8
             # cache: quantised on the way, and read by the e4m3 decode kernel)
-            rope_kv_cache_write_(cache, x4, cos, sin, pos.positions, pos.index, self.hl, KV, 1)
-            o = kv_cache_attend(x4[:, :, :self.hl], cache, causal=True, kv_len=pos.kv_len)
+            rope_kv_cache_write_(cache, x4, cos, sin, pos.positions, pos.index, self.hl, KV, 1, per_row=pos.per_row)
+            o = kv_cache_attend(x4[:, :, :self.hl], cache, causal=True, kv_len=pos.kv_len, per_row=pos.per_row)
             a = reduce_from_tp(linear(o.reshape(B, T, self.hl * hd), self.wo), tp_group)
             n2, h2 = rms_norm(a, self.ffn_norm, c.norm_eps, residual=h)
             f = glu(linear(copy_to_tp(n2, tp_group), self.w13), "gelu_tanh")
@@ -540,10 +540,16 @@ class Gemma(tnn.Module):
         return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.embed.device, dtype=self.embed.dtype,
                        quant=kv_cache_quant(kv_cache))
 
-    def step(self, ids, cache, pos):
+    ragged_decode = True   # per-sequence positions (infer.RaggedDecodeState) through step / step_graph
+
+    def step(self, ids, cache, pos, last=None):
+        """``last`` (int64 [B], a right-padded ragged prompt): the logits of position last[b] of each
+        sequence (gathered before the head) instead of the last position's."""
+        from ..ops.layout import gather_rows
         from ..parallel.tensor_parallel import gather_vocab_logits
         n = self.hidden(ids, cache, pos)
-        return gather_vocab_logits(linear(n[:, -1:], self.embed), self.tp_group).float()[:, -1]
+        n = n[:, -1:] if last is None else gather_rows(n, last)
+        return gather_vocab_logits(linear(n, self.embed), self.tp_group).float()[:, -1]
 
     def step_graph(self, ids, cache, state):
         """One-token decode step with every position on the device (HIP-graph capturable,
@@ -556,11 +562,13 @@ class Gemma(tnn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None):
-        """KV-cached MQA decoding (the reference re-runs the window per token, gemma.ipynb:608-630)."""
+                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None, prompt_lens=None,
+                 pad_token_id=0):
+        """KV-cached MQA decoding (the reference re-runs the window per token, gemma.ipynb:608-630).
+        ``prompt_lens``: a right-padded batch of prompts of different lengths (infer/generate.py)."""
         from ..infer.generate import generate
         return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
-                        sampler=sampler, kv_cache=kv_cache)
+                        sampler=sampler, kv_cache=kv_cache, prompt_lens=prompt_lens, pad_token_id=pad_token_id)
 
     def flops_per_token(self, T):
         c = self.c

@@ -27,6 +27,9 @@ from ..ops.attention import attention_dropout, kv_cache_attend, kv_cache_write
 from ..ops.misc import dropout
 from ..utils.grad import mark_ready
 
+_RAGGED = ("GPT: ragged batches (prompt_lens / per-sequence positions) are not covered: positions are a learned "
+           "table added at the embedding and the model has no step_graph; pass equal-length prompts")
+
 
 @dataclass
 class GPTConfig:
@@ -163,15 +166,17 @@ class GPT(tnn.Module):
         return KVCache(c.num_layers, B, Tmax, c.num_heads, c.emb_dim // c.num_heads,
                        device=self.token_embed.device, dtype=self.token_embed.dtype, quant=kv_cache_quant(kv_cache))
 
-    def step(self, ids, cache, pos):
+    def step(self, ids, cache, pos, last=None):
         """Write ids' K/V at cache rows [pos, pos+T) (learned positions pos..pos+T-1), return the
-        last position's logits [B, V]."""
+        last position's logits [B, V]. Ragged batches (``last``) are not covered."""
+        if last is not None:
+            raise NotImplementedError(_RAGGED)
         h = self.hidden(ids, cache, pos)
         return linear(h[:, -1:], self.lm_head).float()[:, -1]
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, greedy=True, temperature=1.0, top_k=None, generator=None,
-                 eos_token_id=None, stats=None, sampler=None, kv_cache=None):
+                 eos_token_id=None, stats=None, sampler=None, kv_cache=None, prompt_lens=None, pad_token_id=0):
         """gpt-jax.ipynb:821-829 (greedy by default; ``sampler``: an infer.Sampler instead). While prompt + new tokens fit the learned
         position table (block_size) this is KV-cached: one prefill, then one token per step. Past
         block_size the reference crops the window to the last block_size tokens, which shifts
@@ -180,6 +185,8 @@ class GPT(tnn.Module):
         e4m3 cache."""
         from ..infer.generate import generate
         from ..infer.sampling import sample
+        if prompt_lens is not None:
+            raise NotImplementedError(_RAGGED)
         was = self.training
         self.eval()
         n_cached = max(0, min(max_new_tokens, self.c.block_size - idx.shape[1]))

@@ -31,6 +31,7 @@ from ..infer.sampling import sample  # noqa: F401  (re-exported: reference-style
 from ..ops import attention_packed, embedding, linear, linear_cross_entropy, rms_norm, rope_packed_
 from ..ops.linear import swiglu_mlp
 from ..ops.attention import kv_cache_attend, kv_cache_write, rope_kv_cache_write_
+from ..ops.layout import gather_rows
 from ..ops.rope import RopeCache, apply_rope
 from ..utils.grad import mark_ready
 
@@ -114,8 +115,8 @@ class LlamaBlock(nn.Module):
             cos, sin = RopeCache.get(pos.max_len, hd, c.rope_theta, qkv.device, c.ref_freqs)
             # one launch: RoPE on q (in place) and k, k/v rows into the cache at pos.index (an fp8
             # cache: quantised on the way, and read by the e4m3 decode kernel)
-            rope_kv_cache_write_(kv_cache, x4, cos, sin, pos.positions, pos.index, H, KV, 0)
-            o = kv_cache_attend(x4[:, :, :H], kv_cache, causal=True, kv_len=pos.kv_len)
+            rope_kv_cache_write_(kv_cache, x4, cos, sin, pos.positions, pos.index, H, KV, 0, per_row=pos.per_row)
+            o = kv_cache_attend(x4[:, :, :H], kv_cache, causal=True, kv_len=pos.kv_len, per_row=pos.per_row)
             return linear(o.reshape(B, T, H * hd), self.wo)
         if kv_cache is None and self.cp_group is not None:
             # sequence slice at offset rank*T: RoPE at global positions, attention over all
@@ -253,10 +254,14 @@ class Llama3(nn.Module):
         return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.tok_embeddings.device,
                        dtype=self.tok_embeddings.dtype, quant=kv_cache_quant(kv_cache))
 
-    def step(self, ids, cache, pos):
-        """Write ids' K/V at cache rows [pos, pos+T), return the last position's logits [B, V]."""
+    ragged_decode = True   # per-sequence positions (infer.RaggedDecodeState) through step / step_graph
+
+    def step(self, ids, cache, pos, last=None):
+        """Write ids' K/V at cache rows [pos, pos+T), return the last position's logits [B, V].
+        ``last`` (int64 [B], a right-padded ragged prompt): the logits of position last[b] of each
+        sequence, gathered before the head."""
         n = self.hidden(ids, cache, pos)
-        return self.logits(n[:, -1:]).float()[:, -1]
+        return self.logits(n[:, -1:] if last is None else gather_rows(n, last)).float()[:, -1]
 
     def step_graph(self, ids, cache, state: DecodeState):
         """One-token decode step with every position on the device (HIP-graph capturable;
@@ -268,12 +273,14 @@ class Llama3(nn.Module):
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,
-                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None):
+                 top_p=None, eos_token_id=None, stats=None, sampler=None, kv_cache=None, prompt_lens=None,
+                 pad_token_id=0):
         """KV-cached sampling (reference: llama3/LLaMA-jax.ipynb:499-511, categorical at T=1,
-        full re-forward per token; its cache path :816-819 was never exercised)."""
+        full re-forward per token; its cache path :816-819 was never exercised). ``prompt_lens``: a
+        right-padded batch of prompts of different lengths (infer/generate.py)."""
         from ..infer.generate import generate
         return generate(self, ids, max_new_tokens, temperature, top_k, top_p, greedy, eos_token_id, generator, stats,
-                        sampler=sampler, kv_cache=kv_cache)
+                        sampler=sampler, kv_cache=kv_cache, prompt_lens=prompt_lens, pad_token_id=pad_token_id)
 
     # ------------------------------------------------------- reference layout I/O
     def to_reference_params(self):

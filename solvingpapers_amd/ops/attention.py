@@ -425,18 +425,27 @@ def _decode_ok(q, k, v):
                and t.data_ptr() % 8 == 0 for t in (q, k, v))
 
 
-def decode_attention(q, k, v, causal=True, scale=None, nsplit=0, kv_len=None):
+def decode_attention(q, k, v, causal=True, scale=None, nsplit=0, kv_len=None, per_row=False):
     """Few new query rows against a KV cache: q [B,Tq,H,hd], k/v [B,Tk,Hkv,hd] (cache views,
     the last Tq cache rows are the query tokens). Split-K HIP kernel (csrc/kernels/decode.hip)
     when Tq * H / Hkv <= 16, else the flash kernel. Inference only (no autograd).
 
     ``kv_len`` (device int32 [1]): k/v are whole cache buffers and only the first *kv_len
-    rows are valid -- the form a captured hipGraph decode step replays at every position."""
+    rows are valid -- the form a captured hipGraph decode step replays at every position.
+    ``per_row`` (ragged batch): ``kv_len`` is int32 [B] and sequence b counts its own first
+    kv_len[b] rows. On the CPU both forms run the pure-torch oracles (ops/reference.py)."""
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if per_row and kv_len is None:
+        raise ValueError("decode_attention: per_row needs kv_len (int32 [B])")
     if _decode_ok(q, k, v):
-        return _ext.ops().attn_decode(q, k, v, scale, causal, int(nsplit), kv_len)[0]
+        return _ext.ops().attn_decode(q, k, v, scale, causal, int(nsplit), kv_len, per_row)[0]
     if kv_len is not None:
-        raise ValueError("decode_attention: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
+        if q.is_cuda:
+            raise ValueError("decode_attention: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
+        if per_row:
+            return reference.attention_per_row(q, k, v, kv_len, causal, scale)[0]
+        n = min(int(kv_len.reshape(-1)[0]), k.shape[1])
+        return reference.attention(q, k[:, :n], v[:, :n], causal, scale)[0]
     return flash_attention(q.contiguous(), k, v, causal, scale)
 
 
@@ -500,16 +509,20 @@ def kv_cache_write(cache, k, v, pos):
         s[:, :, pos:pos + T] = xs
 
 
-def rope_kv_cache_write_(cache, x4, cos, sin, positions, index, n_heads, n_kv_heads, mode):
+def rope_kv_cache_write_(cache, x4, cos, sin, positions, index, n_heads, n_kv_heads, mode, per_row=False):
     """Graph decode prologue on a packed qkv buffer x4 [B, T, H + 2 Hkv, hd]: RoPE on the q heads in
     place and on the k heads, k / v rows into ``cache`` (bf16 pair or :class:`KV8`) at row
-    ``*index + t``, one launch, every position read on the device."""
-    if isinstance(cache, KV8):
+    ``*index + t``, one launch, every position read on the device. ``per_row`` (ragged batch):
+    ``index`` is int64 [B] and sequence b writes at ``index[b] + t``. CPU tensors take the
+    pure-torch oracle (reference.rope_kv_write)."""
+    if not x4.is_cuda:
+        reference.rope_kv_write(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mode, per_row)
+    elif isinstance(cache, KV8):
         _ext.ops().rope_kv_write_q8_(x4, cos, sin, positions, index, cache.kq, cache.ks, cache.vq, cache.vs,
-                                     n_heads, n_kv_heads, mode)
+                                     n_heads, n_kv_heads, mode, per_row)
     else:
         kc, vc = cache
-        _ext.ops().rope_kv_write_(x4, cos, sin, positions, index, kc, vc, n_heads, n_kv_heads, mode)
+        _ext.ops().rope_kv_write_(x4, cos, sin, positions, index, kc, vc, n_heads, n_kv_heads, mode, per_row)
 
 
 def _decode_q8_ok(q, cache, n):
@@ -523,7 +536,7 @@ def _decode_q8_ok(q, cache, n):
             and q.data_ptr() % 8 == 0)
 
 
-def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=None, fresh=None):
+def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=None, fresh=None, per_row=False):
     """q [B, Tq, H, hd] against rows [0, n) of ``cache`` (``n`` None: the whole buffers, with a device
     ``kv_len``), whose last Tq rows are the query tokens.
 
@@ -531,23 +544,28 @@ def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=
     A :class:`KV8` layer: ``fresh`` = this step's bf16 (k, v) when they are the whole context (a
     prompt prefill at position 0) is attended directly; else attn_decode_q8 over the e4m3 rows when the
     decode kernel applies (Tq * H / Hkv <= 16, hd 64 / 128 / 256, bf16 q on the GPU); else rows [0, n)
-    are dequantised and take :func:`decode_attention`'s route (``kv_len`` cannot apply there)."""
+    are dequantised and take :func:`decode_attention`'s route (``kv_len`` applies there only on the
+    CPU, through the oracle). ``per_row``: ``kv_len`` is int32 [B], one length per sequence."""
     if not isinstance(cache, KV8):
         kc, vc = cache
         if n is not None:
             kc, vc = kc[:, :n], vc[:, :n]
-        return decode_attention(q, kc, vc, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len)
+        return decode_attention(q, kc, vc, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len,
+                                per_row=per_row)
+    if per_row and kv_len is None:
+        raise ValueError("kv_cache_attend: per_row needs kv_len (int32 [B])")
     if fresh is not None:
         return decode_attention(q, fresh[0], fresh[1], causal=causal, scale=scale, nsplit=nsplit)
     rows = cache.max_len if n is None else n
     if _decode_q8_ok(q, cache, rows):
         sc = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
         return _ext.ops().attn_decode_q8(q, cache.kq[:, :rows], cache.ks[:, :, :rows], cache.vq[:, :rows],
-                                         cache.vs[:, :, :rows], sc, causal, int(nsplit), kv_len)[0]
-    if kv_len is not None:
+                                         cache.vs[:, :, :rows], sc, causal, int(nsplit), kv_len, per_row)[0]
+    if kv_len is not None and q.is_cuda:
         raise ValueError("kv_cache_attend: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
     k, v = cache.dequantized(rows)
-    return decode_attention(q, k, v, causal=causal, scale=scale, nsplit=nsplit)
+    # on the CPU a kv_len (scalar or per row) takes decode_attention's oracle over the dequantised rows
+    return decode_attention(q, k, v, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len, per_row=per_row)
 
 
 def mla_decode_attention(q_abs, q_rope, cc, cr, scale, kv_len=0, kv_len_t=None, nsplit=0):

@@ -31,6 +31,16 @@ def transpose2d(x: torch.Tensor) -> torch.Tensor:
     return x.transpose(-1, -2).contiguous()
 
 
+def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """x [B, T, D], idx int64 [B] (each in [0, T)) -> [B, 1, D]: row idx[b] of each batch, the last real
+    position of each right-padded prompt. One HIP launch reading idx on the device (graph-safe); the
+    kernel needs 16-byte rows and raises otherwise. CPU: torch indexing."""
+    if x.is_cuda:
+        return _ext.ops().gather_rows(x, idx)
+    from . import reference
+    return reference.gather_rows(x, idx)
+
+
 def wgrad_nt_ok(dy2: torch.Tensor, x2: torch.Tensor) -> bool:
     # the transpose kernel moves 16-byte units along both axes: token count, N and K all % 8
     # (MTP heads feed T - k tokens, e.g. 8190)

@@ -239,6 +239,60 @@ def attn_decode_q8(q, kq, ks, vq, vs, causal=True, scale=None):
     return attention(_f(q), dequant_kv8(kq, ks), dequant_kv8(vq, vs), causal, scale)
 
 
+def attention_per_row(q, k, v, kv_len, causal=True, scale=None):
+    """Ragged-batch decode attention (attn_decode / attn_decode_q8 with ``per_row``): sequence b
+    attends over its own cache rows [0, min(kv_len[b], Tk)), whose last Tq rows are its query
+    tokens. k / v are the whole cache buffers [B, Tk, Hkv, hd]. Returns (out, lse)."""
+    lens = [min(int(n), k.shape[1]) for n in torch.as_tensor(kv_len).reshape(-1).tolist()]
+    if len(lens) != q.shape[0]:
+        raise ValueError(f"attention_per_row: {len(lens)} lengths for a batch of {q.shape[0]}")
+    parts = [attention(q[b:b + 1], k[b:b + 1, :n], v[b:b + 1, :n], causal, scale) for b, n in enumerate(lens)]
+    return torch.cat([o for o, _ in parts]), torch.cat([l for _, l in parts])
+
+
+def rope_kv_write(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mode=0, per_row=False):
+    """Decode-step prologue (csrc/kernels/rope.hip rope_kv_write_ / rope_kv_write_q8_) on a packed qkv
+    buffer x4 [B, T, H + 2 Hkv, hd]: RoPE at ``positions`` [B, T] on the q heads (in place) and on
+    the k heads (mode 0 interleaved, 1 rotate_half); k / v rows into ``cache`` at row index + t
+    (``per_row``: index[b] + t). ``cache`` is a (kc, vc) pair [B, Tmax, Hkv, hd] or a KV8-like object
+    (kq / ks / vq / vs), which stores :func:`quant_kv8` of the value the pair would hold. Rows
+    outside [0, Tmax) are dropped."""
+    B, T = x4.shape[0], x4.shape[1]
+    H, KV = n_heads, n_kv_heads
+    pos = positions.reshape(B, T)
+    x4[:, :, :H] = rope(x4[:, :, :H], cos, sin, interleaved=mode == 0, positions=pos)
+    k = rope(x4[:, :, H:H + KV], cos, sin, interleaved=mode == 0, positions=pos)
+    v = x4[:, :, H + KV:]
+    idx = [int(i) for i in index.reshape(-1).tolist()]
+    if per_row and len(idx) != B:
+        raise ValueError(f"rope_kv_write: per_row needs {B} indices, got {len(idx)}")
+    rows = idx if per_row else [idx[0]] * B
+    fp8 = hasattr(cache, "kq")
+    if fp8:
+        (kq, ks), (vq, vs) = quant_kv8(k), quant_kv8(v)
+        Tmax = cache.kq.shape[1]
+    else:
+        Tmax = cache[0].shape[1]
+    for b in range(B):
+        for t in range(T):
+            r = rows[b] + t
+            if not 0 <= r < Tmax:
+                continue
+            if fp8:
+                cache.kq.view(torch.uint8)[b, r] = kq.view(torch.uint8)[b, t]
+                cache.vq.view(torch.uint8)[b, r] = vq.view(torch.uint8)[b, t]
+                cache.ks[b, :, r] = ks[b, :, t]
+                cache.vs[b, :, r] = vs[b, :, t]
+            else:
+                cache[0][b, r] = k[b, t]
+                cache[1][b, r] = v[b, t]
+
+
+def gather_rows(x, idx):
+    """x [B, T, D], idx int64 [B] -> [B, 1, D]: row idx[b] of each batch (csrc/kernels/layout.hip)."""
+    return x[torch.arange(x.shape[0], device=x.device), idx][:, None]
+
+
 def sample_probs(logits, temperature=1.0, top_k=None, top_p=None):
     """Unnormalised fp64 sampling weights [B, V] in vocabulary order (0 for dropped tokens): the
     distribution csrc/kernels/sample.hip draws from. Order: raw logit descending, ties by ascending

@@ -7,7 +7,8 @@ usage: python tools/bench_kernels.py [--iters N] [--only name,name]
 kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only sample`` runs just the
 token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
 ``--only decode_attn`` runs just the decode-attention rows: attn_decode_q8 over an fp8 KV cache against
-attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes.
+attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes, then
+the per_row (ragged batch) form of both kernels at batch 16: equal lengths and lengths spread 1:4.
 """
 import argparse
 import json
@@ -210,6 +211,49 @@ def decode_attn_rows(iters, rounds=3):
         del cb, cf, arms
 
 
+def decode_attn_per_row_rows(iters, rounds=3):
+    """The per_row (ragged batch) form of both decode-attention kernels at the batch-16 LLaMA3-8B shapes:
+    ``scalar`` is a one-entry device kv_len (what the uniform graph decode launches), ``equal`` a kv_len
+    [B] with every length Tk, ``spread`` lengths spaced evenly from Tk / 4 to Tk (1:4). Ring, A B C C B A
+    order and medians as in decode_attn_rows. ``time_vs_scalar`` compares at equal work; the spread rows
+    count only the valid rows' bytes in their GB/s (the empty splits of short rows still launch)."""
+    from solvingpapers_amd.ops import reference as R
+    ops = _ext.ops()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for H, Hkv, hd, B, Tk in [s for s in DECODE_ATTN_SHAPES if s[3] > 1 and s[2] == 128]:
+        ring = max(4, -(-(320 << 20) // (2 * B * Tk * Hkv * (hd + 1))))
+        q = torch.randn(B, 1, H, hd, device=DEV, dtype=BF, generator=g)
+        k, v = (torch.randn(B, Tk, Hkv, hd, device=DEV, dtype=BF, generator=g) for _ in range(2))
+        (kq, ks), (vq, vs) = R.quant_kv8(k), R.quant_kv8(v)
+        sc = hd ** -0.5
+        lens = {"scalar": torch.tensor([Tk], device=DEV, dtype=torch.int32),
+                "equal": torch.full((B,), Tk, device=DEV, dtype=torch.int32),
+                "spread": torch.linspace(Tk / 4, Tk, B, device=DEV).round().int()}
+        rows = {a: (B * Tk if a != "spread" else int(lens[a].sum())) for a in lens}
+        for fmt, row_bytes in (("bf16", Hkv * hd * 2), ("fp8", Hkv * (hd + 1))):
+            if fmt == "bf16":
+                ringc = [(k.clone(), v.clone()) for _ in range(ring)]
+                call = lambda c, a: ops.attn_decode(q, c[0], c[1], sc, True, 0, lens[a], a != "scalar")
+            else:
+                ringc = [tuple(t.clone() for t in (kq, ks, vq, vs)) for _ in range(ring)]
+                call = lambda c, a: ops.attn_decode_q8(q, *c, sc, True, 0, lens[a], a != "scalar")
+            arms = {a: _graphed(lambda a=a: [call(c, a) for c in ringc]) for a in lens}
+            ms = {a: [] for a in arms}
+            for _ in range(rounds):
+                for arm in ("scalar", "equal", "spread", "spread", "equal", "scalar"):
+                    ms[arm].append(timed(arms[arm], iters) / ring)
+            med = {a: sorted(t)[len(t) // 2] for a, t in ms.items()}
+            name = "attn_decode" if fmt == "bf16" else "attn_decode_q8"
+            for a in arms:
+                nbytes = 2 * rows[a] * row_bytes
+                print(json.dumps({"kernel": f"{name}_{a}_B{B}_Tk{Tk}_H{H}kv{Hkv}_hd{hd}", "ms": round(med[a], 5),
+                                  "GB": round(nbytes / 1e9, 4), "kv_GB_per_s": round(nbytes / med[a] / 1e6, 1),
+                                  "min_ms": round(min(ms[a]), 5), "max_ms": round(max(ms[a]), 5), "ring": ring,
+                                  **({"time_vs_scalar": round(med[a] / med["scalar"], 3)} if a != "scalar" else {})}),
+                      flush=True)
+            del ringc, arms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -223,6 +267,7 @@ def main():
         sample_rows(a.iters)
     if not only or "decode_attn" in only:
         decode_attn_rows(a.iters)
+        decode_attn_per_row_rows(a.iters)
     for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn"} else cases()).items():
         if only and name not in only:
             continue
