@@ -793,6 +793,10 @@ at::Tensor wgrad8(const at::Tensor& dy, const at::Tensor& x, const c10::optional
                   (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat),
               "wgrad8: out [N, K] bf16/fp32 contiguous");
   if (N == 0 || K == 0) return out;
+  if (T == 0) {   // no tokens: the slice length below would be 0 and S its quotient
+    if (!accumulate) out.zero_();
+    return out;
+  }
   auto st = stream();
   const int tiles = cdiv(N, 256) * cdiv(K, 256);
   int S = (int)splits;
