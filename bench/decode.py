@@ -3,7 +3,8 @@
 
 Default: LLaMA3-8B shape, bf16, random-init weights, synthetic prompt. Reports prefill
 tok/s and decode tok/s (all sequences); one JSON line. ``--weights fp8`` decodes from the
-block-scaled e4m3 images of infer.quantize_decode_weights (prefill stays on bf16);
+block-scaled e4m3 images of infer.quantize_decode_weights, ``--weights mxfp4`` from its OCP MXFP4 images
+(prefill stays on bf16);
 ``--kv-cache fp8`` keeps the KV cache as e4m3 rows with per-row E8M0 scales (infer/cache.py) and
 decodes with attn_decode_q8 -- the cache's size is reported as ``kv_cache_bytes`` either way. The
 ``--sampler`` picks how the next token is drawn: ``greedy`` (argmax, captured with
@@ -57,8 +58,9 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--graph", action="store_true", help="HIP-graph decode (one replay per token)")
     ap.add_argument("--set", action="append", default=[], help="config override key=value")
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: decode products read e4m3 weight images (128x128 E8M0 block scales)")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                    help="fp8: decode products read e4m3 weight images (128x128 E8M0 block scales); "
+                         "mxfp4: e2m1 images (1x32 E8M0 block scales)")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: e4m3 KV cache with one E8M0 scale per (batch, kv head, token) row")
     ap.add_argument("--sampler", choices=["greedy", "eager", "fused"], default="greedy",
@@ -77,9 +79,9 @@ def main(argv=None):
         a.batch, a.prompt = len(lens), max(lens)
     m = build(a.model, a.layers, a.set).eval()
     extra = {} if lens is None else {"prompt_lens": lens}
-    if a.weights == "fp8":
+    if a.weights != "bf16":
         from solvingpapers_amd.infer import quantize_decode_weights
-        rep = quantize_decode_weights(m)
+        rep = quantize_decode_weights(m) if a.weights == "fp8" else quantize_decode_weights(m, fmt=a.weights)
         extra = {"weights": rep["format"], "image_bytes": rep["image_bytes"],
                  "quantized_params": len(rep["quantized"]), "bf16_params": len(rep["bf16"])}
     kvc = None if a.kv_cache == "bf16" else a.kv_cache     # None: every call as before the option existed

@@ -1,9 +1,14 @@
 // Weight-streaming GEMV for decode: y[M, N] = x[M, K] @ W[N, K]^T, x / y bf16, fp32 accumulation,
-// M <= 4 (the decode batch), dense and grouped (MoE), for two weight formats:
+// M <= 4 (the decode batch), dense and grouped (MoE), for three weight formats:
 //   bf16   W as stored (gemv, grouped_gemv);
 //   e4m3   the fp8 weight-only image: Wq OCP e4m3 [N, K], S uint8 E8M0 [N/128, K/128] (DeepSeek-V3's
 //          128 x 128 block scales, as quant_weight_fp8_blk writes them), w = q * 2^(S - 127); half the
 //          bytes (gemv_w8, grouped_gemv_w8). N % 128 == 0 and K % 128 == 0.
+//   mxfp4  the OCP MXFP4 weight-only image: Wq uint8 [N, K/2], two e2m1 codes per byte (k = 2j in bits
+//          3:0, k = 2j + 1 in bits 7:4; code = sign << 3 | mag, mag 0..7 = 0, .5, 1, 1.5, 2, 3, 4, 6),
+//          S uint8 E8M0 [N, K/32], one scale per 32 consecutive k of one row, as quant_weight_mxfp4
+//          (quant_mxfp4.hip) writes them; 4.25 bits per weight (gemv_w4, grouped_gemv_w4).
+//          K % 32 == 0 and N % 4 == 0.
 //
 // A decode step multiplies a handful of token rows by every projection matrix: pure weight
 // streaming (LLaMA3-8B: 16 GB per token), so the kernel is built for HBM, not for MFMA:
@@ -32,17 +37,32 @@
 //    once per weight row and reused by all token rows;
 //  * the block exponents are 1..254 (quant_weight_fp8_blk clamps to +-126), so S << 23 is the
 //    scale's fp32 bit pattern.
+// For mxfp4:
+//  * a 16-byte load is 32 weights = exactly one MX block, so every (lane, row, load) has its own scale
+//    byte: one byte load per weight row and pass, 64 consecutive bytes per wave and row;
+//  * v_cvt_scalef32_pk_bf16_fp4 turns one byte (two codes) times a float scale into a bf16 pair, low
+//    nibble first; e2m1 times a power of two is exact in bf16. Scale bytes are 1..254 as above
+//    (quant_weight_mxfp4 clamps the exponent to [-126, 125]);
+//  * a pass is 2048 weights of a row, and U = 8 is chosen by measurement alone
+//    (profiles/mxfp4_decode_gemv.txt, section 2): up to K = 14336 no row enters the 8-pass loop, all of
+//    LLaMA3-8B runs through the single-pass loop behind it, and that loop, compiled behind the 8-pass
+//    one, timed faster than U = 2 and U = 4 and than the same loop standing alone. Why is not known, so
+//    rerun that section after a toolchain update. (8192 x 28672, where the 8-pass loop runs, is timed too.)
+//    The grouped kernel keeps one pass in flight (UG = 1): with 8 it needs 256 VGPRs, one wave per SIMD,
+//    and dsv3_style decode was 17 % slower than on fp8 images.
 #include "spa_common.h"
 
 namespace spa {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// Weight formats. elem: storage type; raw: one 16-byte load = H * 8 weights; BLOCKED: whole 128 x 128
-// blocks, contiguous (no row tail to clamp, row stride K); scale_row: the block scales of weight row
-// `row` of the expert whose scale rows start at `base`; scale: the scale byte of the chunk at
-// k + ahead (ahead: a compile-time multiple of 128, kept apart so that the look-ahead loads share
-// one address register); prepare: raw chunk -> H bf16x8 in K order.
+// Weight formats. elem: storage type, holding 1 << SH weights; raw: one 16-byte load = H * 8 weights;
+// BLOCKED: whole scale blocks, contiguous (no row tail to clamp, row stride K >> SH); ROW_SCALES: every
+// weight row of a wave has its own scale byte per chunk (else the wave's rows share one); U, UG: passes in
+// flight of the dense and the grouped kernel (their template argument); scale_row: the scales of weight
+// row `row` of expert `e` (N rows each); scale: the scale byte of row `row` + r's chunk at k + ahead
+// (ahead: a compile-time multiple of the block width, kept apart so that the look-ahead loads share one
+// address register); prepare: raw chunk -> H bf16x8 in K order.
 // ROW_AT_A_TIME<M, RW>: the dense kernel's statement order for a chunk (accumulate_rows). The
 // arithmetic is the same either way; hipcc's load schedule is not, and it decides 1-5 % of the time
 // of these kernels (profiles/gemv_unify.txt). e4m3 converts one weight row at a time (8 VGPRs of
@@ -52,24 +72,24 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct WBf16 {
   using elem = bf16;
   using raw = bf16x8;
-  static constexpr int H = 1;
-  static constexpr bool BLOCKED = false;
+  static constexpr int H = 1, SH = 0, U = 4, UG = 4;
+  static constexpr bool BLOCKED = false, ROW_SCALES = false;
   template <int M, int RW> static constexpr bool ROW_AT_A_TIME = M * RW == 16;
-  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t*, long, int, int) { return nullptr; }
-  static __device__ __forceinline__ uint8_t scale(const uint8_t*, int, int) { return 0; }
+  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t*, int, int, int, int) { return nullptr; }
+  static __device__ __forceinline__ uint8_t scale(const uint8_t*, int, int, int, int) { return 0; }
   static __device__ __forceinline__ void prepare(const raw& q, uint8_t, bf16x8 (&w)[H]) { w[0] = q; }
 };
 
 struct WE4m3 {
   using elem = uint8_t;
   using raw = u32x4;
-  static constexpr int H = 2;
-  static constexpr bool BLOCKED = true;
+  static constexpr int H = 2, SH = 0, U = 4, UG = 4;
+  static constexpr bool BLOCKED = true, ROW_SCALES = false;
   template <int M, int RW> static constexpr bool ROW_AT_A_TIME = true;
-  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t* s, long base, int row, int K) {
-    return s + (base + (row >> 7)) * (K >> 7);
+  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t* s, int e, int N, int row, int K) {
+    return s + ((long)e * (N >> 7) + (row >> 7)) * (K >> 7);
   }
-  static __device__ __forceinline__ uint8_t scale(const uint8_t* sr, int k, int ahead) {
+  static __device__ __forceinline__ uint8_t scale(const uint8_t* sr, int, int, int k, int ahead) {
     return sr[(k >> 7) + (ahead >> 7)];
   }
   // dword j holds k = 4j .. 4j + 3, low half first
@@ -82,6 +102,32 @@ struct WE4m3 {
                                      __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[j], sc, true), 0, 1, 2, 3);
     w[0] = __builtin_shufflevector(p[0], p[1], 0, 1, 2, 3, 4, 5, 6, 7);
     w[1] = __builtin_shufflevector(p[2], p[3], 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+};
+
+struct WMxfp4 {
+  using elem = uint8_t;
+  using raw = u32x4;
+  static constexpr int H = 4, SH = 1, U = 8, UG = 1;
+  static constexpr bool BLOCKED = true, ROW_SCALES = true;
+  template <int M, int RW> static constexpr bool ROW_AT_A_TIME = true;
+  static __device__ __forceinline__ const uint8_t* scale_row(const uint8_t* s, int e, int N, int row, int K) {
+    return s + ((long)e * N + row) * (K >> 5);
+  }
+  static __device__ __forceinline__ uint8_t scale(const uint8_t* sr, int r, int K, int k, int ahead) {
+    return sr[r * (K >> 5) + (k >> 5) + (ahead >> 5)];
+  }
+  // dword j holds k = 8j .. 8j + 7: byte b is k = 8j + 2b (low nibble) and 8j + 2b + 1 (high nibble)
+  static __device__ __forceinline__ void prepare(const raw& q, uint8_t sb, bf16x8 (&w)[H]) {
+    const float sc = __builtin_bit_cast(float, (unsigned)sb << 23);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bf16x4 lo = __builtin_shufflevector(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[j], sc, 0),
+                                                __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[j], sc, 1), 0, 1, 2, 3);
+      const bf16x4 hi = __builtin_shufflevector(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[j], sc, 2),
+                                                __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q[j], sc, 3), 0, 1, 2, 3);
+      w[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
   }
 };
 
@@ -104,13 +150,14 @@ __device__ __forceinline__ void accumulate_rows(float (&acc)[MB][RW], const bf16
                                                 const long ldx, const int mn,
                                                 const typename F::elem* const (&wr)[RW],
                                                 const uint8_t* __restrict__ sr, const int K, const int lane) {
-  static_assert(128 % RW == 0, "a wave's rows must share one 128-row scale block");
+  static_assert(F::ROW_SCALES || 128 % RW == 0, "a wave's rows must share one 128-row scale block");
   using raw = typename F::raw;
   constexpr int CH = 8 * F::H, PASS = 64 * CH;  // weights per lane / per wave and pass
+  constexpr int SH = F::SH, SR = F::ROW_SCALES ? RW : 1;  // SR: scale bytes per chunk
   auto load = [](const typename F::elem* p) {
     return NT ? __builtin_nontemporal_load(reinterpret_cast<const raw*>(p)) : *reinterpret_cast<const raw*>(p);
   };
-  auto consume = [&](const int k, const raw* wv, const uint8_t sc) {
+  auto consume = [&](const int k, const raw* wv, const uint8_t (&sc)[SR]) {
     bf16x8 xv[MB][F::H], wp[RW][F::H];
     auto load_x = [&](const int m) {
 #pragma unroll
@@ -122,7 +169,7 @@ __device__ __forceinline__ void accumulate_rows(float (&acc)[MB][RW], const bf16
       for (int m = 0; m < MB; ++m) load_x(m);
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
-        F::prepare(wv[r], sc, wp[r]);
+        F::prepare(wv[r], sc[F::ROW_SCALES ? r : 0], wp[r]);
 #pragma unroll
         for (int m = 0; m < MB; ++m)
 #pragma unroll
@@ -131,7 +178,7 @@ __device__ __forceinline__ void accumulate_rows(float (&acc)[MB][RW], const bf16
       return;
     }
 #pragma unroll
-    for (int r = 0; r < RW; ++r) F::prepare(wv[r], sc, wp[r]);
+    for (int r = 0; r < RW; ++r) F::prepare(wv[r], sc[F::ROW_SCALES ? r : 0], wp[r]);
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
       if (m < mn) {
@@ -146,21 +193,25 @@ __device__ __forceinline__ void accumulate_rows(float (&acc)[MB][RW], const bf16
   int k = CH * lane;
   for (; k + (U - 1) * PASS < K; k += U * PASS) {
     raw wv[U][RW];
-    uint8_t sc[U];
+    uint8_t sc[U][SR];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
 #pragma unroll
-      for (int r = 0; r < RW; ++r) wv[u][r] = load(wr[r] + k + u * PASS);
-      sc[u] = F::scale(sr, k, u * PASS);
+      for (int r = 0; r < RW; ++r) wv[u][r] = load(wr[r] + (k >> SH) + ((u * PASS) >> SH));
+#pragma unroll
+      for (int r = 0; r < SR; ++r) sc[u][r] = F::scale(sr, r, K, k, u * PASS);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) consume(k + u * PASS, wv[u], sc[u]);
   }
   for (; k < K; k += PASS) {
     raw wv[RW];
+    uint8_t sc[SR];
 #pragma unroll
-    for (int r = 0; r < RW; ++r) wv[r] = load(wr[r] + k);
-    consume(k, wv, F::scale(sr, k, 0));
+    for (int r = 0; r < RW; ++r) wv[r] = load(wr[r] + (k >> SH));
+#pragma unroll
+    for (int r = 0; r < SR; ++r) sc[r] = F::scale(sr, r, K, k, 0);
+    consume(k, wv, sc);
   }
 }
 
@@ -176,9 +227,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ x, c
   const typename F::elem* wr[RW];
 #pragma unroll
   for (int r = 0; r < RW; ++r)  // tail rows: duplicate, not stored
-    wr[r] = w + (long)(F::BLOCKED ? row0 + r : min(row0 + r, N - 1)) * (F::BLOCKED ? (long)K : ldw);
+    wr[r] = w + (long)(F::BLOCKED ? row0 + r : min(row0 + r, N - 1)) * (F::BLOCKED ? (long)(K >> F::SH) : ldw);
   float acc[M][RW] = {};
-  const uint8_t* sr = F::scale_row(s, 0, row0, K);
+  const uint8_t* sr = F::scale_row(s, 0, N, row0, K);
   accumulate_rows<F, M, RW, U, true, F::template ROW_AT_A_TIME<M, RW>>(acc, x, 0, ldx, M, wr, sr, K, lane);
 #pragma unroll
   for (int m = 0; m < M; ++m)
@@ -195,7 +246,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16* __restrict__ x, c
 // ACTIVE expert's weights once instead. Grid: experts x column chunks; a wave owns RW weight rows
 // (output columns) and walks the expert's token rows in groups of 4 (re-reading its weight rows
 // from L2 past 4 rows, hence plain loads). Experts with no rows exit at once (the row counts live
-// on the device: no host sync). x [A, K], w [E, N, K], s [E, N/128, K/128], all contiguous.
+// on the device: no host sync). x [A, K], w [E, N, K] (or its image), s, all contiguous.
 template <class F, int RW, int U>
 __global__ __launch_bounds__(256) void grouped_gemv_kernel(const bf16* __restrict__ x,
                                                            const typename F::elem* __restrict__ w,
@@ -212,8 +263,8 @@ __global__ __launch_bounds__(256) void grouped_gemv_kernel(const bf16* __restric
   const typename F::elem* wr[RW];
 #pragma unroll
   for (int r = 0; r < RW; ++r)
-    wr[r] = w + ((long)e * N + (F::BLOCKED ? row0 + r : min(row0 + r, N - 1))) * K;
-  const uint8_t* sr = F::scale_row(s, (long)e * (N >> 7), row0, K);
+    wr[r] = w + ((long)e * N + (F::BLOCKED ? row0 + r : min(row0 + r, N - 1))) * (K >> F::SH);
+  const uint8_t* sr = F::scale_row(s, e, N, row0, K);
   for (int m0 = r_begin; m0 < r_end; m0 += MB) {
     const int mn = min(MB, r_end - m0);
     float acc[MB][RW] = {};
@@ -229,11 +280,13 @@ __global__ __launch_bounds__(256) void grouped_gemv_kernel(const bf16* __restric
   }
 }
 
-// Host-side argument checks, shared by the four ops. `lead`: 0 dense, 1 grouped (a leading expert dim).
-// The weight operand: bf16 w [.., N, K], or with `s` its e4m3 image wq [.., N, K] + s [.., N/128, K/128].
-static void check_weight(const char* op, const at::Tensor& w, const at::Tensor* s, int64_t lead) {
+// Host-side argument checks, shared by the six ops. `lead`: 0 dense, 1 grouped (a leading expert dim).
+// The weight operand: bf16 w [.., N, K]; or with `s` an image of it: e4m3 wq [.., N, K] + s [.., N/128,
+// K/128], or mxfp4 wq uint8 [.., N, K/2] + s [.., N, K/32]. Returns K, the weights per row.
+template <class F>
+static int64_t check_weight(const char* op, const at::Tensor& w, const at::Tensor* s, int64_t lead) {
   TORCH_CHECK(w.is_cuda() && w.dim() == lead + 2, op, ": w must be a ", lead + 2, "-D HIP tensor");
-  const int64_t N = w.size(lead), K = w.size(lead + 1);
+  const int64_t N = w.size(lead), K = w.size(lead + 1) << F::SH;
   TORCH_CHECK(N < ((int64_t)1 << 31) && K < ((int64_t)1 << 31) && ((uintptr_t)w.data_ptr() % 16) == 0, op,
               ": w must be 16-byte aligned");
   if (!s) {
@@ -241,23 +294,31 @@ static void check_weight(const char* op, const at::Tensor& w, const at::Tensor* 
     // a dense weight may be a row-strided view (a slice of a wider buffer)
     TORCH_CHECK(K % 8 == 0 && (lead ? w.is_contiguous() : w.stride(1) == 1 && w.stride(0) % 8 == 0), op,
                 ": rows must be 16-byte aligned with K % 8 == 0", lead ? ", w contiguous" : "");
-    return;
+    return K;
   }
-  TORCH_CHECK(s->is_cuda() && s->device() == w.device() && w.scalar_type() == at::kFloat8_e4m3fn &&
-                  s->scalar_type() == at::kByte,
-              op, ": wq float8_e4m3fn, s uint8 (E8M0) HIP tensors on one device");
+  constexpr bool W4 = F::ROW_SCALES;
+  TORCH_CHECK(s->is_cuda() && s->device() == w.device() &&
+                  w.scalar_type() == (W4 ? at::kByte : at::kFloat8_e4m3fn) && s->scalar_type() == at::kByte,
+              op, ": wq ", W4 ? "uint8 (two e2m1 codes per byte)" : "float8_e4m3fn",
+              ", s uint8 (E8M0) HIP tensors on one device");
   TORCH_CHECK(w.is_contiguous() && s->is_contiguous(), op, ": wq, s contiguous");
-  TORCH_CHECK(N % 128 == 0 && K % 128 == 0, op, ": N % 128 == 0 and K % 128 == 0 (got N = ", N, ", K = ", K, ")");
-  TORCH_CHECK(s->dim() == lead + 2 && s->size(lead) == N / 128 && s->size(lead + 1) == K / 128 &&
+  if (W4) {
+    TORCH_CHECK(N % 4 == 0 && K % 32 == 0, op, ": N % 4 == 0 and K % 32 == 0 (got N = ", N, ", K = ", K, ")");
+  } else {
+    TORCH_CHECK(N % 128 == 0 && K % 128 == 0, op, ": N % 128 == 0 and K % 128 == 0 (got N = ", N, ", K = ", K, ")");
+  }
+  const int64_t sn = W4 ? N : N / 128, sk = W4 ? K / 32 : K / 128;
+  TORCH_CHECK(s->dim() == lead + 2 && s->size(lead) == sn && s->size(lead + 1) == sk &&
                   (lead == 0 || s->size(0) == w.size(0)),
-              op, ": s must be [", (lead ? "E, " : ""), "N/128, K/128]");
+              op, ": s must be [", (lead ? "E, " : ""), W4 ? "N, K/32]" : "N/128, K/128]");
+  return K;
 }
 
 // x: bf16 [rows, K] on w's device, rows 16-byte aligned (K % 8 == 0 is the weight's check); grouped: contiguous
-static void check_x(const char* op, const at::Tensor& x, const at::Tensor& w, int64_t lead) {
+static void check_x(const char* op, const at::Tensor& x, const at::Tensor& w, int64_t K, int64_t lead) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.device() == w.device(), op,
               ": x must be a bf16 HIP tensor on w's device");
-  TORCH_CHECK(x.dim() == 2 && x.size(1) == w.size(lead + 1), op, ": x [rows, K], w [.., N, K]");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K, op, ": x [rows, K], w [.., N, K]");
   TORCH_CHECK((lead ? x.is_contiguous() : x.stride(1) == 1 && x.stride(0) % 8 == 0) &&
                   ((uintptr_t)x.data_ptr() % 16) == 0,
               op, ": x rows must be 16-byte aligned", lead ? ", x contiguous" : "");
@@ -265,23 +326,23 @@ static void check_x(const char* op, const at::Tensor& x, const at::Tensor& w, in
 
 template <class F, int M>
 static void launch_gemv(const at::Tensor& x, const at::Tensor& w, const at::Tensor* s, at::Tensor& y) {
-  const int N = w.size(0), K = w.size(1);
+  const int N = w.size(0), K = x.size(1);
   const auto xp = (const bf16*)x.data_ptr();
   const auto wp = (const typename F::elem*)w.data_ptr();
   const auto sp = s ? (const uint8_t*)s->data_ptr() : nullptr;
   const auto yp = (bf16*)y.data_ptr();
   if (N >= 8192)
-    gemv_kernel<F, M, 4, 4><<<cdiv(cdiv(N, 4), 4), 256, 0, stream()>>>(xp, wp, sp, yp, N, K, x.stride(0), w.stride(0));
+    gemv_kernel<F, M, 4, F::U><<<cdiv(cdiv(N, 4), 4), 256, 0, stream()>>>(xp, wp, sp, yp, N, K, x.stride(0), w.stride(0));
   else
-    gemv_kernel<F, M, 2, 4><<<cdiv(cdiv(N, 2), 4), 256, 0, stream()>>>(xp, wp, sp, yp, N, K, x.stride(0), w.stride(0));
+    gemv_kernel<F, M, 2, F::U><<<cdiv(cdiv(N, 2), 4), 256, 0, stream()>>>(xp, wp, sp, yp, N, K, x.stride(0), w.stride(0));
 }
 
-// x [M, K] bf16 (row stride ldx), w [N, K] (+ s [N/128, K/128]) -> y [M, N] bf16; M <= 4
+// x [M, K] bf16 (row stride ldx), w [N, K] (or its image wq + s) -> y [M, N] bf16; M <= 4
 template <class F>
 static at::Tensor gemv_op(const char* op, const at::Tensor& x, const at::Tensor& w, const at::Tensor* s) {
-  check_weight(op, w, s, 0);
-  check_x(op, x, w, 0);
-  const int M = x.size(0), N = w.size(0), K = w.size(1);
+  const int K = check_weight<F>(op, w, s, 0);
+  check_x(op, x, w, K, 0);
+  const int M = x.size(0), N = w.size(0);
   TORCH_CHECK(M >= 1 && M <= 4, op, ": M must be 1..4");
   DeviceGuard g(x.device());
   auto y = at::empty({M, N}, x.options());
@@ -296,12 +357,11 @@ static at::Tensor gemv_op(const char* op, const at::Tensor& x, const at::Tensor&
   return y;
 }
 
-// x [A, K] expert-sorted rows, w [E, N, K] (+ s [E, N/128, K/128]), offsets [E+1] (device) -> y [A, N]
+// x [A, K] expert-sorted rows, w [E, N, K] (or its image wq + s), offsets [E+1] (device) -> y [A, N]
 template <class F>
 static at::Tensor grouped_gemv_op(const char* op, const at::Tensor& x, const at::Tensor& w, const at::Tensor* s,
                                   const at::Tensor& offsets) {
-  check_weight(op, w, s, 1);
-  check_x(op, x, w, 1);
+  check_x(op, x, w, check_weight<F>(op, w, s, 1), 1);
   TORCH_CHECK(offsets.is_cuda() && offsets.device() == x.device() && offsets.scalar_type() == at::kInt &&
                   offsets.is_contiguous() && offsets.numel() == w.size(0) + 1,
               op, ": offsets int32 [E+1] on the device");
@@ -312,7 +372,7 @@ static at::Tensor grouped_gemv_op(const char* op, const at::Tensor& x, const at:
   if (K == 0) return y.zero_();
   const int nwb = cdiv(cdiv(N, 2), 4);
   TORCH_CHECK((int64_t)E * nwb < (int64_t)1 << 31, op, ": grid too large");
-  grouped_gemv_kernel<F, 2, 4><<<E * nwb, 256, 0, stream()>>>(
+  grouped_gemv_kernel<F, 2, F::UG><<<E * nwb, 256, 0, stream()>>>(
       (const bf16*)x.data_ptr(), (const typename F::elem*)w.data_ptr(), s ? (const uint8_t*)s->data_ptr() : nullptr,
       (bf16*)y.data_ptr(), offsets.data_ptr<int>(), N, K);
   SPA_LAUNCH_CHECK();
@@ -331,6 +391,14 @@ at::Tensor grouped_gemv_w8(const at::Tensor& x, const at::Tensor& wq, const at::
   return grouped_gemv_op<WE4m3>("grouped_gemv_w8", x, wq, &s, offsets);
 }
 
+at::Tensor gemv_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& s) {
+  return gemv_op<WMxfp4>("gemv_w4", x, wq, &s);
+}
+at::Tensor grouped_gemv_w4(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& s,
+                           const at::Tensor& offsets) {
+  return grouped_gemv_op<WMxfp4>("grouped_gemv_w4", x, wq, &s, offsets);
+}
+
 }  // namespace spa
 
 TORCH_LIBRARY_FRAGMENT(spa, m) {
@@ -338,10 +406,14 @@ TORCH_LIBRARY_FRAGMENT(spa, m) {
   m.def("grouped_gemv(Tensor x, Tensor w, Tensor offsets) -> Tensor");
   m.def("gemv_w8(Tensor x, Tensor wq, Tensor s) -> Tensor");
   m.def("grouped_gemv_w8(Tensor x, Tensor wq, Tensor s, Tensor offsets) -> Tensor");
+  m.def("gemv_w4(Tensor x, Tensor wq, Tensor s) -> Tensor");
+  m.def("grouped_gemv_w4(Tensor x, Tensor wq, Tensor s, Tensor offsets) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("gemv", &spa::gemv);
   m.impl("grouped_gemv", &spa::grouped_gemv);
   m.impl("gemv_w8", &spa::gemv_w8);
   m.impl("grouped_gemv_w8", &spa::grouped_gemv_w8);
+  m.impl("gemv_w4", &spa::gemv_w4);
+  m.impl("grouped_gemv_w4", &spa::grouped_gemv_w4);
 }

@@ -300,7 +300,7 @@ def _gemv_ok(x, w, b) -> bool:
 
 def _w8_cpu_ok(x, w, b) -> bool:
     """:func:`_gemv_ok`'s conditions on the CPU: a decode-shaped inference product there reads a
-    weight's fp8 decode image through the oracle, so a quantised model decodes the same on both."""
+    weight's decode image (fp8 or MXFP4) through the oracle, so a quantised model decodes the same on both."""
     if x.is_cuda or b is not None or w.dim() != 2 or not x.is_floating_point():
         return False
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
@@ -395,27 +395,35 @@ def _fp8_ok(x, w) -> bool:
 
 def _decode_linear(x, w, b):
     """x w^T of a decode-shaped inference product on the weight-streaming GEMV, or None where the
-    product is not one. The weight's fp8 decode image where it carries one (``gemv_w8``; on the
-    CPU, :func:`_w8_cpu_ok`, the dequantised oracle product), else the bf16 master (``gemv``)."""
-    has_image = getattr(w, "_spa_w8", None) is not None
+    product is not one. The weight's fp8 or MXFP4 decode image where it carries one (``gemv_w8`` /
+    ``gemv_w4``; on the CPU, :func:`_w8_cpu_ok`, the dequantised oracle product), else the bf16 master
+    (``gemv``)."""
+    # quantize_decode_weights keeps one image per parameter; were both attached, fp8 (the default) wins
+    if getattr(w, "_spa_w8", None) is not None:
+        name, image = "gemv_w8", "w8_image"
+    elif getattr(w, "_spa_w4", None) is not None:
+        name, image = "gemv_w4", "w4_image"
+    else:
+        name, image = "gemv", None
     if _gemv_ok(x, w, b):
-        op = _ext.ops().gemv_w8 if has_image else _ext.ops().gemv
-    elif has_image and _w8_cpu_ok(x, w, b):
-        from .reference import gemv_w8 as op
+        op = getattr(_ext.ops(), name)
+    elif image is not None and _w8_cpu_ok(x, w, b):
+        from . import reference
+        op = getattr(reference, name)
     else:
         return None
-    from .moe import w8_image
+    from . import moe
     x2 = x.reshape(-1, x.shape[-1])
     if x2.stride(0) % 8:                          # the kernels read 16-byte aligned rows
         x2 = x2.contiguous()
-    y = op(x2, *w8_image(w)) if has_image else op(x2, w)
+    y = op(x2, *getattr(moe, image)(w)) if image is not None else op(x2, w)
     return y.to(x.dtype).view(*x.shape[:-1], w.shape[0])
 
 
 def linear(x, w, b=None, fp8=False):
     """y = x w^T (+ b). ``fp8``: e4m3 forward / dX on hipBLASLt with row-wise scales (dims
     multiples of 16; else bf16). A decode-shaped inference product goes to the GEMV kernels
-    (csrc/kernels/gemv.hip), ``fp8`` or not, and reads the weight's fp8 decode image
+    (csrc/kernels/gemv.hip), ``fp8`` or not, and reads the weight's fp8 or MXFP4 decode image
     (infer.quantize_decode_weights) where it carries one (:func:`_decode_linear`)."""
     y = _decode_linear(x, w, b)
     if y is not None:

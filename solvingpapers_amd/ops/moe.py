@@ -272,16 +272,23 @@ def grouped_linear(xp, W, plan: MoEPlan, fp8: bool = False):
     active expert's weights once (``grouped_gemv``, csrc/kernels/gemv.hip) instead of paying a
     256-row MFMA tile per expert for one or two tokens. Where ``W`` carries an fp8 decode image
     (infer.quantize_decode_weights) that product reads the image instead
-    (``grouped_gemv_w8``, same file; on the CPU the dequantised oracle product)."""
+    (``grouped_gemv_w8``, same file; on the CPU the dequantised oracle product); likewise an MXFP4
+    decode image (``fmt="mxfp4"``: ``grouped_gemv_w4``)."""
     if not torch.is_grad_enabled() and xp.shape[0] <= GEMV_MAX_ROWS:          # decode
         has_image = getattr(W, "_spa_w8", None) is not None
+        has_w4 = getattr(W, "_spa_w4", None) is not None
         if xp.is_cuda and xp.dtype == torch.bfloat16 and W.dtype == torch.bfloat16:
             if has_image:
                 return ops().grouped_gemv_w8(xp.contiguous(), *w8_image(W), plan.offsets)
+            if has_w4:
+                return ops().grouped_gemv_w4(xp.contiguous(), *w4_image(W), plan.offsets)
             return ops().grouped_gemv(xp.contiguous(), W.contiguous(), plan.offsets)
         if has_image and not xp.is_cuda:
             from .reference import grouped_gemv_w8
             return grouped_gemv_w8(xp, *w8_image(W), plan.offsets).to(xp.dtype)
+        if has_w4 and not xp.is_cuda:
+            from .reference import grouped_gemv_w4
+            return grouped_gemv_w4(xp, *w4_image(W), plan.offsets).to(xp.dtype)
     if fp8:
         return _GroupedLinearFP8Fn.apply(xp, W, plan)
     return _GroupedLinearFn.apply(xp, W, plan)
@@ -377,6 +384,31 @@ def w8_image(W):
         raise RuntimeError(
             f"fp8 decode image of parameter '{name}' is stale (the weight was updated or moved after "
             "quantize_decode_weights): call quantize_decode_weights(model) again, or clear_decode_weights(model)")
+    return wq, s
+
+
+def quant_weight_mxfp4(W):
+    """The MXFP4 decode image of W [E, N, K], K % 32 == 0: (wq uint8 [E, N, K/2], s uint8 E8M0
+    [E, N, K/32]), the layout and rule of ops/reference.py ``quant_mxfp4``: the single-pass HIP quantizer
+    (csrc/kernels/quant_mxfp4.hip) for bf16 HIP tensors, the bit-exact torch formula otherwise."""
+    if W.is_cuda and W.dtype == torch.bfloat16:
+        return tuple(ops().quant_weight_mxfp4(W.detach().contiguous()))
+    from .reference import quant_mxfp4
+    return quant_mxfp4(W)
+
+
+def w4_image(W):
+    """The MXFP4 decode image (wq, s) that infer.quantize_decode_weights(fmt="mxfp4") attached to ``W``,
+    or None; a stale one raises, exactly as :func:`w8_image`."""
+    im = getattr(W, "_spa_w4", None)
+    if im is None:
+        return None
+    wq, s, version, ptr, name = im
+    if W._version != version or W.data_ptr() != ptr:
+        raise RuntimeError(
+            f"mxfp4 decode image of parameter '{name}' is stale (the weight was updated or moved after "
+            "quantize_decode_weights): call quantize_decode_weights(model, fmt=\"mxfp4\") again, or "
+            "clear_decode_weights(model)")
     return wq, s
 
 

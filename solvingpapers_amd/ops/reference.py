@@ -214,6 +214,66 @@ def grouped_gemv_w8(x, wq, s, offsets):
     return out
 
 
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # OCP e2m1 magnitudes by code
+
+
+def quant_mxfp4(W):
+    """The OCP MXFP4 image of W [.., N, K], K % 32 == 0 (bf16 values in any floating dtype):
+    (wq uint8 [.., N, K/2], s uint8 E8M0 [.., N, K/32]) with w ~= value(code) * 2^(s - 127). Byte j of a
+    row holds the code of k = 2j in bits 3:0 and of k = 2j + 1 in bits 7:4; a code is sign << 3 | mag,
+    mag 0..7 = 0, .5, 1, 1.5, 2, 3, 4, 6. One scale per 32 consecutive k of one row: e the smallest
+    integer with amax <= 6 * 2^e (read off amax's fp32 bits: amax = m 2^p needs e = p - 2 when m <= 1.5,
+    else p - 1), clamped to [-126, 125], 0 for an all-zero block. |w| / 2^e, exact in fp32, goes to the
+    nearest magnitude (saturating at 6), a tie to the even code; the sign bit is the weight's own.
+    Bit-exact with quant_weight_mxfp4 (csrc/kernels/quant_mxfp4.hip).
+
+    Requantising a dequantised image returns the same VALUES bit for bit, but not always the same bytes: a
+    block whose amax rounded down to 3 * 2^e is rescaled to 6 * 2^(e - 1) (every code's value doubles
+    exactly), and a block that rounded to all zeros takes the zero block's scale. The bytes are a fixed
+    point from that second image on (tests/test_quant_w4_cpu.py)."""
+    *lead, N, K = W.shape
+    assert K % 32 == 0, K
+    t = W.detach().float().reshape(*lead, N, K // 32, 32)
+    a = t.abs()
+    amax = a.amax(-1)
+    bits = amax.contiguous().view(torch.int32)
+    e = ((bits >> 23) & 0xff) - 127 - torch.where((bits & 0x7fffff) <= 0x400000, 2, 1)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(-126, 125)
+    v = a * torch.exp2(-e.float())[..., None]
+    code = ((v > 0.25).int() + (v >= 0.75).int() + (v > 1.25).int() + (v >= 1.75).int() + (v > 2.5).int()
+            + (v >= 3.5).int() + (v > 5.0).int()) | (torch.signbit(t).int() << 3)
+    code = code.reshape(*lead, N, K // 2, 2)
+    wq = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)
+    return wq, (e + 127).to(torch.uint8)
+
+
+def dequant_w4(wq, s):
+    """fp32 weights of an MXFP4 image (:func:`quant_mxfp4`'s layout): wq uint8 [.., N, K/2],
+    s uint8 [.., N, K/32] -> value(code) * 2^(s - 127), [.., N, K]. Every value is exact in bf16."""
+    *lead, N, K2 = wq.shape
+    lut = torch.tensor(E2M1 + tuple(-m for m in E2M1), dtype=torch.float32, device=wq.device)
+    q = wq.to(torch.int64)
+    v = lut[torch.stack((q & 0xf, q >> 4), -1)].reshape(*lead, N, K2 // 16, 32)
+    return (v * torch.exp2(s.float() - 127)[..., None]).reshape(*lead, N, 2 * K2)
+
+
+def gemv_w4(x, wq, s):
+    """x [M, K] times the dequantised MXFP4 image [N, K]^T, fp32 (csrc/kernels/gemv.hip)."""
+    return x.float() @ dequant_w4(wq, s).t()
+
+
+def grouped_gemv_w4(x, wq, s, offsets):
+    """Expert-sorted rows x [A, K] times the dequantised MXFP4 image of their expert, wq [E, N, K/2],
+    offsets [E+1]: fp32 [A, N]."""
+    off = offsets.tolist()
+    w = dequant_w4(wq, s)
+    out = torch.zeros(x.shape[0], wq.shape[1], dtype=torch.float32, device=x.device)
+    for e in range(len(off) - 1):
+        if off[e + 1] > off[e]:
+            out[off[e]:off[e + 1]] = x[off[e]:off[e + 1]].float() @ w[e].t()
+    return out
+
+
 def quant_kv8(x):
     """fp8 KV-cache rows: x [B, T, Hkv, hd] -> (q float8_e4m3fn [B, T, Hkv, hd], s uint8 E8M0
     [B, Hkv, T]) with x ~= q * 2^(s - 127), one scale per (batch, kv head, token) over the row's hd

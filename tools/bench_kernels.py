@@ -3,9 +3,9 @@ as achieved HBM bandwidth (ideal bytes / time). Run under ``rocprofv3 --pmc`` fo
 
 usage: python tools/bench_kernels.py [--iters N] [--only name,name]
 
-``--only gemv`` runs just the decode GEMV rows: the fp8 weight-only kernel (gemv_w8) against the bf16
-kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only sample`` runs just the
-token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
+``--only gemv`` runs just the decode GEMV rows: the fp8 and MXFP4 weight-only kernels (gemv_w8, gemv_w4)
+against the bf16 kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only sample`` runs
+just the token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
 ``--only decode_attn`` runs just the decode-attention rows: attn_decode_q8 over an fp8 KV cache against
 attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes, then
 the per_row (ragged batch) form of both kernels at batch 16: equal lengths and lengths spread 1:4.
@@ -111,36 +111,42 @@ def _graphed(fn):
 
 
 def gemv_rows(iters, rounds=3):
-    """gemv_w8 next to gemv, same process, arms alternated A B B A per round. Every call reads another
-    copy of the weight out of a ring larger than the 256 MB last-level cache (both arms: 32 copies at
-    least), as a decode step does, where each matrix is read once per token; one pass over the ring is one
-    HIP-graph replay. Reported: GB/s of WEIGHT bytes and the fp8 / bf16 time ratio (< 1: the fp8 kernel
-    is faster)."""
-    from solvingpapers_amd.ops.moe import quant_weight_fp8_blk_uncached
+    """gemv_w8 and gemv_w4 next to gemv, same process, arms alternated A B C C B A per round. Every call
+    reads another copy of the weight out of a ring larger than the 256 MB last-level cache (all arms: 32
+    copies at least, >= 0.5 GB of the smallest format), as a decode step does, where each matrix is read once
+    per token; one pass over the ring is one HIP-graph replay. Reported: GB/s of WEIGHT bytes (scales
+    included), the fp8 / bf16 and mxfp4 / bf16 time ratios and mxfp4 / fp8 (< 1: the first is faster)."""
+    from solvingpapers_amd.ops.moe import quant_weight_fp8_blk_uncached, quant_weight_mxfp4
     ops = _ext.ops()
     g = torch.Generator(device=DEV).manual_seed(0)
     for N, K in GEMV_SHAPES:
-        ring = max(32, -(-(1 << 30) // (N * K)))             # >= 1 GB of fp8 bytes, 2 GB of bf16
+        ring = max(32, -(-(1 << 30) // (N * K)))             # >= 1 GB of fp8 bytes, 2 GB of bf16, 0.5 GB of mxfp4
         w = torch.randn(N, K, device=DEV, dtype=BF, generator=g)
         wq, _, s, _ = quant_weight_fp8_blk_uncached(w[None])
+        w4, s4 = quant_weight_mxfp4(w[None])
         wb = [w.clone() for _ in range(ring)]
         wf = [(wq[0].clone(), s[0].clone()) for _ in range(ring)]
+        w4s = [(w4[0].clone(), s4[0].clone()) for _ in range(ring)]
         for M in (1, 4):
             x = torch.randn(M, K, device=DEV, dtype=BF, generator=g)
             arms = {"bf16": _graphed(lambda: [ops.gemv(x, wi) for wi in wb]),
-                    "fp8": _graphed(lambda: [ops.gemv_w8(x, q, si) for q, si in wf])}
-            ms = {"bf16": [], "fp8": []}
+                    "fp8": _graphed(lambda: [ops.gemv_w8(x, q, si) for q, si in wf]),
+                    "mxfp4": _graphed(lambda: [ops.gemv_w4(x, q, si) for q, si in w4s])}
+            ms = {a: [] for a in arms}
             for _ in range(rounds):
-                for arm in ("bf16", "fp8", "fp8", "bf16"):
+                for arm in ("bf16", "fp8", "mxfp4", "mxfp4", "fp8", "bf16"):
                     ms[arm].append(timed(arms[arm], iters) / ring)
-            mb, mf = (sorted(ms[a])[len(ms[a]) // 2] for a in ("bf16", "fp8"))
-            for arm, m_, nbytes in (("gemv", mb, N * K * 2), ("gemv_w8", mf, N * K + N * K // 16384)):
-                print(json.dumps({"kernel": f"{arm}_M{M}_{N}x{K}", "ms": round(m_, 5), "GB": round(nbytes / 1e9, 4),
-                                  "weight_GB_per_s": round(nbytes / m_ / 1e6, 1),
-                                  "min_ms": round(min(ms["bf16" if arm == "gemv" else "fp8"]), 5),
-                                  "max_ms": round(max(ms["bf16" if arm == "gemv" else "fp8"]), 5),
-                                  **({"time_vs_bf16": round(mf / mb, 3)} if arm == "gemv_w8" else {})}), flush=True)
-        del wb, wf
+            med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+            for arm, key, nbytes in (("gemv", "bf16", N * K * 2), ("gemv_w8", "fp8", N * K + N * K // 16384),
+                                     ("gemv_w4", "mxfp4", N * K // 2 + N * K // 32)):
+                ratios = {} if key == "bf16" else {"time_vs_bf16": round(med[key] / med["bf16"], 3)}
+                if key == "mxfp4":
+                    ratios["time_vs_fp8"] = round(med[key] / med["fp8"], 3)
+                print(json.dumps({"kernel": f"{arm}_M{M}_{N}x{K}", "ms": round(med[key], 5), "GB": round(nbytes / 1e9, 4),
+                                  "weight_GB_per_s": round(nbytes / med[key] / 1e6, 1),
+                                  "min_ms": round(min(ms[key]), 5), "max_ms": round(max(ms[key]), 5), **ratios}),
+                      flush=True)
+        del wb, wf, w4s
 
 
 def sample_rows(iters, rounds=3):
