@@ -11,7 +11,9 @@ decodes with attn_decode_q8 -- the cache's size is reported as ``kv_cache_bytes`
 ``--graph``), ``eager`` (infer.sample(): topk / sort / softmax / multinomial launches between the replays) or ``fused``
 (infer.Sampler: one kernel, captured in the graph). ``--prompt-lens a,b,c,...`` decodes a ragged batch (one
 prompt length per sequence, right-padded; per-sequence positions: GraphDecoder(ragged=True) with ``--graph``) and
-adds ``prompt_lens`` to the result line. The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
+adds ``prompt_lens`` to the result line. ``--page-size N`` decodes from a paged KV cache (infer/cache.py PagedKVCache,
+bf16 pages of N rows) of ``--pages N`` pages per layer (default: enough for every slot's prompt + new rows);
+``kv_cache_bytes`` is then the pools' size. The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
 from __future__ import annotations
 
 import argparse
@@ -72,13 +74,23 @@ def main(argv=None):
     ap.add_argument("--prompt-lens", default=None,
                     help="a,b,c,...: one prompt length per sequence (ragged batch, right-padded to the longest; "
                          "sets --batch and --prompt); with --graph the step is captured over per-sequence positions")
+    ap.add_argument("--page-size", type=int, default=None,
+                    help="paged KV cache: rows per page (a power of two in [16, 256]); LLaMA3 / Gemma, bf16 cache")
+    ap.add_argument("--pages", type=int, default=None,
+                    help="pages per layer of the paged cache, the null page included (default: batch * pages per "
+                         "sequence + 1)")
     a = ap.parse_args(argv)
+    if a.pages is not None and a.page_size is None:
+        ap.error("--pages needs --page-size")
+    pkw = {} if a.page_size is None else {"page_size": a.page_size, "num_pages": a.pages}
     lens = None
     if a.prompt_lens is not None:
         lens = [int(x) for x in a.prompt_lens.split(",")]
         a.batch, a.prompt = len(lens), max(lens)
     m = build(a.model, a.layers, a.set).eval()
     extra = {} if lens is None else {"prompt_lens": lens}
+    if pkw:
+        extra.update(page_size=a.page_size)
     if a.weights != "bf16":
         from solvingpapers_amd.infer import quantize_decode_weights
         rep = quantize_decode_weights(m) if a.weights == "fp8" else quantize_decode_weights(m, fmt=a.weights)
@@ -100,20 +112,31 @@ def main(argv=None):
     if a.graph:
         from solvingpapers_amd.infer import GraphDecoder
         dec = GraphDecoder(m, a.batch, a.prompt + a.new, greedy=a.sampler == "greedy", sampler=sampler, **ckw,
-                           **({} if lens is None else {"ragged": True}))
+                           **pkw, **({} if lens is None else {"ragged": True}))
         cache_bytes = dec.cache.nbytes() if hasattr(dec.cache, "nbytes") else None
+        if pkw:
+            extra.update(num_pages=dec.cache.num_pages)
         dec.generate(ids[:, :64], 4, **kw, **wkw)  # warm-up of the eager prefill path
         if sampler is not None:
             sampler.reseed(a.seed)
         out = dec.generate(ids, a.new, stats=st, **kw, **rkw)
     else:
         kw = dict(kw, greedy=a.sampler == "greedy", sampler=sampler, **ckw)
-        row = m.new_cache(a.batch, 1, **ckw)     # generate() allocates prompt + new rows of this size
-        cache_bytes = row.nbytes() * (a.prompt + a.new) if hasattr(row, "nbytes") else None
-        m.generate(ids[:, :64], 4, **kw, **wkw)  # warm-up (kernels, allocator)
+        gen = m.generate
+        if pkw:    # the models' generate() carries no paging arguments: the driver itself
+            from solvingpapers_amd.infer import generate
+            gen = lambda *args, **k: generate(m, *args, **k, **pkw)
+            pool = m.new_cache(a.batch, a.prompt + a.new, **ckw, **pkw)   # what generate() allocates
+            cache_bytes = pool.nbytes()
+            extra.update(num_pages=pool.num_pages)
+            del pool
+        else:
+            row = m.new_cache(a.batch, 1, **ckw)     # generate() allocates prompt + new rows of this size
+            cache_bytes = row.nbytes() * (a.prompt + a.new) if hasattr(row, "nbytes") else None
+        gen(ids[:, :64], 4, **kw, **wkw)         # warm-up (kernels, allocator)
         if sampler is not None:
             sampler.reseed(a.seed)
-        out = m.generate(ids, a.new, stats=st, **kw, **rkw)
+        out = gen(ids, a.new, stats=st, **kw, **rkw)
     torch.cuda.synchronize()
     print(json.dumps({"metric": "decode tokens/s", "model": a.model, "graph": a.graph, "batch": a.batch, "prompt": a.prompt,
                       "new_tokens": st.new_tokens, "prefill_tok_s": round(st.prefill_tok_s, 1),

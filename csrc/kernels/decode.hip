@@ -21,9 +21,11 @@
 // scale) KV cache.
 #include "spa_common.h"
 #include "fp8_quant.h"
+#include "paged_kv.h"
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 SPA_DEBUG_TU("decode.hip")
 
@@ -47,8 +49,23 @@ constexpr int kKeysPerLoad = 8;
 // keys one 4-wave block covers per load batch: 4 waves x (64 / (hd / 4)) lane groups x 8
 constexpr int keys_per_batch(int hd) { return 4 * (256 / hd) * kKeysPerLoad; }
 
-template <int HD, int R, bool FUSED>
-__global__ __launch_bounds__(256) void attn_decode_kernel(DecodeParams p) {
+// attn_decode_paged: the same parameters over a paged cache. k / v are the page pools (skt / svt the
+// pool-row stride, skb / svb unused), Tk the logical row bound.
+struct DecodePagedParams : DecodeParams {
+  PagedTable tb;
+};
+
+// A/B switch for the paged lookup (tools/build_variant.sh nolook -DSPA_PAGED_LOOKAHEAD=0): 1 (default) looks a
+// load batch's page ids up one batch ahead; 0 looks them up in front of the batch's own K/V loads.
+#ifndef SPA_PAGED_LOOKAHEAD
+#define SPA_PAGED_LOOKAHEAD 1
+#endif
+
+// PAGED: a key's row address comes through the block table (p.tb); everything else, the floating-point
+// code included, is the same source, and PAGED = false compiles to what it was before the flag. The
+// in-launch merge (FUSED) is not instantiated for PAGED.
+template <int HD, int R, bool FUSED, bool PAGED = false>
+__global__ __launch_bounds__(256) void attn_decode_kernel(std::conditional_t<PAGED, DecodePagedParams, DecodeParams> p) {
   constexpr int KL = HD / 4;        // lanes per key
   constexpr int KPW = 64 / KL;      // keys per wave step
   constexpr int NG = 4 * KPW;       // lane groups per block
@@ -89,8 +106,19 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecodeParams p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[r][j] = 0.f;
   }
-  const bf16* kb = p.k + b * p.skb + hk * p.skh + 4 * sub;
-  const bf16* vb = p.v + b * p.svb + hk * p.svh + 4 * sub;
+  const bf16* kb = p.k + (PAGED ? 0 : b * p.skb) + hk * p.skh + 4 * sub;
+  const bf16* vb = p.v + (PAGED ? 0 : b * p.svb) + hk * p.svh + 4 * sub;
+  // PAGED: the page ids of a load batch are looked up one batch ahead (the first batch's here, beside
+  // the q loads; the next batch's beside this batch's K/V loads), so the dependent table load is off
+  // the K/V round trip of every batch but a block's first. Rows are clamped to k1 - 1 as the K/V loads
+  // are: no table entry past a sequence's valid length is read.
+  [[maybe_unused]] int pg[KPL];
+  if constexpr (PAGED && SPA_PAGED_LOOKAHEAD) {
+    if (k0 < k1) {
+#pragma unroll
+      for (int j = 0; j < KPL; ++j) pg[j] = paged_page(p.tb, b, min(k0 + j * NG + grp, k1 - 1));
+    }
+  }
   // Batches of KPL keys per lane group: every K/V load of a batch is issued before any is
   // consumed (one HBM round trip per batch, 2 * KPL loads in flight per lane), and the batch
   // shares one online-softmax rescale per row. Keys past the split end are clamped on load
@@ -100,9 +128,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecodeParams p) {
     bf16x4 kx[KPL], vx[KPL];
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
-      const long kk = min(base + j * NG + grp, k1 - 1);
+      long kk = min(base + j * NG + grp, k1 - 1);
+      if constexpr (PAGED) kk = paged_pool_row(p.tb, SPA_PAGED_LOOKAHEAD ? pg[j] : paged_page(p.tb, b, kk), kk);
       kx[j] = *reinterpret_cast<const bf16x4*>(kb + kk * p.skt);
       vx[j] = *reinterpret_cast<const bf16x4*>(vb + kk * p.svt);
+    }
+    if constexpr (PAGED && SPA_PAGED_LOOKAHEAD) {
+      if (base + NG * KPL < k1) {
+#pragma unroll
+        for (int j = 0; j < KPL; ++j) pg[j] = paged_page(p.tb, b, min(base + NG * KPL + j * NG + grp, k1 - 1));
+      }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -293,6 +328,22 @@ static int* arrival_counters(const at::Tensor& like, hipStream_t st, int n) {
   return t.data_ptr<int>();
 }
 
+// Split sizing of attn_decode and attn_decode_paged (one function of Tk, B, Hkv, hd and the request, so
+// both cut the same keys into the same splits): nsplit_req <= 0 splits the keys so the grid covers the
+// chip ~2x, each split a whole number of load batches (hd 128: 64 keys = 8 lane groups x 8 keys in flight).
+static void decode_splits(int Tk, int B, int Hkv, int HD, int64_t nsplit_req, int& nsplit, int& chunk) {
+  const int kpb = keys_per_batch(HD);
+  nsplit = (int)nsplit_req;
+  if (nsplit <= 0) {
+    const int want = std::max(1, 512 / std::max(1, B * Hkv));
+    nsplit = std::max(1, std::min(want, cdiv(Tk, kpb)));
+    chunk = cdiv(cdiv(Tk, nsplit), kpb) * kpb;
+  } else {
+    chunk = cdiv(Tk, nsplit);
+  }
+  nsplit = cdiv(Tk, chunk);
+}
+
 // q [B, Tq, H, hd] (Tq * H / Hkv <= 16), k/v [B, Tk, Hkv, hd] strided (cache views); with
 // kv_len (device int32) k/v are the full cache buffers and only rows [0, *kv_len) count, so a
 // decode step can be captured once in a hipGraph and replayed at every position. per_row: kv_len is
@@ -318,19 +369,8 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k, co
   auto out = at::empty({B, Tq, H, HD}, q.options());
   auto lse = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
   if (B * Tq * H == 0) return {out, lse};
-  // split the keys so the grid covers the chip ~2x, each split a whole number of load
-  // batches (hd 128: 64 keys = 8 lane groups x 8 keys in flight)
-  const int kpb = keys_per_batch(HD);
-  int nsplit = (int)nsplit_req;
-  int chunk;
-  if (nsplit <= 0) {
-    const int want = std::max(1, 512 / std::max(1, B * Hkv));
-    nsplit = std::max(1, std::min(want, cdiv(Tk, kpb)));
-    chunk = cdiv(cdiv(Tk, nsplit), kpb) * kpb;
-  } else {
-    chunk = cdiv(Tk, nsplit);
-  }
-  nsplit = cdiv(Tk, chunk);
+  int nsplit, chunk;
+  decode_splits(Tk, B, Hkv, HD, nsplit_req, nsplit, chunk);
   auto part = at::empty({(long)nsplit * B * Tq * H * (HD + 2)}, q.options().dtype(at::kFloat));
   DecodeParams p{};
   p.q = (const bf16*)q.data_ptr(); p.k = (const bf16*)k.data_ptr(); p.v = (const bf16*)v.data_ptr();
@@ -381,6 +421,95 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k, co
   else TORCH_CHECK(false, "attn_decode: head dim must be 64, 128 or 256");
 #undef SPA_DECODE_LAUNCH
 #undef SPA_DECODE_ROWS
+  SPA_LAUNCH_CHECK();
+  return {out, lse};
+}
+
+// attn_decode over a paged cache: kpool / vpool bf16 [num_pages, page_size, Hkv, hd], block_table int32
+// [B, NP] (one table for every layer), Tk the logical row bound (<= NP * page_size; what k.size(1) is to
+// attn_decode, split sizing included). kv_len / per_row as there; without kv_len every sequence attends
+// over Tk rows. Rows at or past a sequence's valid length are never read, nor are their table entries.
+std::vector<at::Tensor> attn_decode_paged(const at::Tensor& q, const at::Tensor& kpool, const at::Tensor& vpool,
+                                          const at::Tensor& block_table, double scale, bool causal,
+                                          int64_t nsplit_req, int64_t Tk64, const c10::optional<at::Tensor>& kv_len,
+                                          bool per_row) {
+  for (auto* t : {&q, &kpool, &vpool}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->dim() == 4,
+                "attn_decode_paged: bf16 q [B,T,H,hd] and pools [num_pages,page_size,Hkv,hd]");
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) % 4 == 0 && t->stride(1) % 4 == 0 && t->stride(0) % 4 == 0 &&
+                    ((uintptr_t)t->data_ptr() % 8) == 0,
+                "attn_decode_paged: rows must be 8-byte aligned and contiguous in hd");
+  }
+  const int B = q.size(0), Tq = q.size(1), H = q.size(2), HD = q.size(3);
+  const int64_t num_pages = kpool.size(0), page = kpool.size(1);
+  const int Hkv = kpool.size(2);
+  TORCH_CHECK(page >= 16 && page <= 256 && (page & (page - 1)) == 0,
+              "attn_decode_paged: page_size must be a power of two in [16, 256], got ", page);
+  TORCH_CHECK(vpool.sizes() == kpool.sizes() && kpool.size(3) == HD && Hkv > 0 && H % Hkv == 0 && num_pages >= 1,
+              "attn_decode_paged: shape mismatch");
+  TORCH_CHECK(kpool.stride(0) == page * kpool.stride(1) && vpool.stride(0) == page * vpool.stride(1),
+              "attn_decode_paged: a pool's pages must be back to back (stride(0) == page_size * stride(1))");
+  TORCH_CHECK(num_pages * page < (1L << 31), "attn_decode_paged: pool rows must fit an int32");
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == q.device() && kpool.device() == q.device() &&
+                  vpool.device() == q.device() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+                  block_table.size(0) == B && block_table.is_contiguous(),
+              "attn_decode_paged: block_table must be a contiguous int32 [B, NP] tensor on q's device");
+  const int64_t NP = block_table.size(1);
+  TORCH_CHECK(Tk64 >= 0 && Tk64 <= NP * page, "attn_decode_paged: Tk = ", Tk64, " outside the table's ", NP * page, " rows");
+  const int Tk = (int)Tk64;
+  TORCH_CHECK(Tq <= Tk, "attn_decode_paged: the cache must hold the query tokens");
+  const int rows = Tq * (H / Hkv);
+  TORCH_CHECK(rows <= kMaxRows, "attn_decode_paged: Tq * H / Hkv must be <= 16 (gather the rows and use flash attention)");
+  TORCH_CHECK(HD == 64 || HD == 128 || HD == 256, "attn_decode_paged: head dim must be 64, 128 or 256");
+  if (kv_len.has_value()) {
+    TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
+                "attn_decode_paged: kv_len must be a device int32 tensor");
+    TORCH_CHECK(!per_row || (kv_len->numel() == B && kv_len->is_contiguous()),
+                "attn_decode_paged: per_row needs one kv_len per sequence (", B, "), got ", kv_len->numel());
+  } else {
+    TORCH_CHECK(!per_row, "attn_decode_paged: per_row needs a device int32 kv_len [B]");
+  }
+  DeviceGuard g(q.device());
+  auto out = at::empty({B, Tq, H, HD}, q.options());
+  auto lse = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
+  if (B * Tq * H == 0) return {out, lse};
+  int nsplit, chunk;
+  decode_splits(Tk, B, Hkv, HD, nsplit_req, nsplit, chunk);
+  auto part = at::empty({(long)nsplit * B * Tq * H * (HD + 2)}, q.options().dtype(at::kFloat));
+  DecodePagedParams p{};
+  p.q = (const bf16*)q.data_ptr(); p.k = (const bf16*)kpool.data_ptr(); p.v = (const bf16*)vpool.data_ptr();
+  p.opart = part.data_ptr<float>();
+  p.mpart = p.opart + (long)nsplit * B * Tq * H * HD;
+  p.lpart = p.mpart + (long)nsplit * B * Tq * H;
+  p.out = (bf16*)out.data_ptr(); p.lse = lse.data_ptr<float>();
+  p.B = B; p.Tq = Tq; p.Tk = Tk; p.H = H; p.Hkv = Hkv; p.nsplit = nsplit; p.chunk = chunk;
+  p.sqb = q.stride(0); p.sqt = q.stride(1); p.sqh = q.stride(2);
+  p.skt = kpool.stride(1); p.skh = kpool.stride(2);  // skb / svb unused: a sequence's rows come through the table
+  p.svt = vpool.stride(1); p.svh = vpool.stride(2);
+  p.sob = out.stride(0); p.sot = out.stride(1); p.soh = out.stride(2);
+  p.scale_log2 = (float)(scale * 1.4426950408889634);
+  p.causal = causal;
+  if (kv_len.has_value()) {
+    p.kv_len = kv_len->data_ptr<int>();
+    p.per_row = per_row;
+  }
+  int lg = 0;
+  while ((1 << lg) < page) ++lg;
+  p.tb = PagedTable{block_table.data_ptr<int>(), (int)NP, lg, (int)num_pages};
+  auto st = stream();
+  const dim3 grid(B * Hkv, nsplit);
+  const int nrows = B * Tq * H;
+#define SPA_DECODE_PAGED_LAUNCH(HDV)                                                                \
+  {                                                                                                \
+    if (rows <= 4) attn_decode_kernel<HDV, 4, false, true><<<grid, 256, 0, st>>>(p);                \
+    else if (rows <= 8) attn_decode_kernel<HDV, 8, false, true><<<grid, 256, 0, st>>>(p);           \
+    else attn_decode_kernel<HDV, 16, false, true><<<grid, 256, 0, st>>>(p);                         \
+    attn_decode_combine_kernel<HDV><<<nrows, 256, 0, st>>>(p);                                     \
+  }
+  if (HD == 64) SPA_DECODE_PAGED_LAUNCH(64)
+  else if (HD == 128) SPA_DECODE_PAGED_LAUNCH(128)
+  else SPA_DECODE_PAGED_LAUNCH(256)
+#undef SPA_DECODE_PAGED_LAUNCH
   SPA_LAUNCH_CHECK();
   return {out, lse};
 }
@@ -685,10 +814,13 @@ std::vector<at::Tensor> attn_decode_q8(const at::Tensor& q, const at::Tensor& kq
 TORCH_LIBRARY_FRAGMENT(spa, m) {
   m.def("attn_decode(Tensor q, Tensor k, Tensor v, float scale, bool causal, int nsplit, Tensor? kv_len=None, "
         "bool per_row=False) -> Tensor[]");
+  m.def("attn_decode_paged(Tensor q, Tensor kpool, Tensor vpool, Tensor block_table, float scale, bool causal, "
+        "int nsplit, int Tk, Tensor? kv_len=None, bool per_row=False) -> Tensor[]");
   m.def("attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, float scale, bool causal, int nsplit, "
         "Tensor? kv_len=None, bool per_row=False) -> Tensor[]");
 }
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("attn_decode", &spa::attn_decode);
+  m.impl("attn_decode_paged", &spa::attn_decode_paged);
   m.impl("attn_decode_q8", &spa::attn_decode_q8);
 }

@@ -11,6 +11,7 @@
 // cos/sin come from an fp32 table [Tmax, hd/2] (L2/LLC resident).
 #include "spa_common.h"
 #include "fp8_quant.h"
+#include "paged_kv.h"
 #include <type_traits>
 
 SPA_DEBUG_TU("rope.hip")
@@ -127,7 +128,18 @@ void rope_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin, co
 // row and the RoPE positions are read from device memory, so a captured hipGraph replays it
 // at every position (replaces rope_ + two index_copy_ launches per layer). Rows past the
 // cache end are dropped.
-template <int MODE>
+//
+// Paged cache (rope_kv_write_paged_, infer/cache.py PagedKVCache): kc / vc are page pools [num_pages,
+// page_size, Hkv, hd], Tmax is the table's NP * page_size logical rows, and logical row r of sequence b
+// goes to pool row bt[b, r >> lg] * page_size + (r & (page_size - 1)). A row outside [0, Tmax) is dropped
+// before the table is read; an unreserved row's entry is 0, the null page, which nothing valid reads
+// (paged_kv.h).
+struct NoTable {};
+
+// PAGED: the k / v destination row comes through the block table (tb; kct / vct are the pool-row stride,
+// kcb / vcb unused); the q-head rotation and all arithmetic are the same source, and PAGED = false
+// compiles to what it was before the flag.
+template <int MODE, bool PAGED = false>
 __global__ __launch_bounds__(256) void rope_kv_write_kernel(bf16* __restrict__ x, const float* __restrict__ cosT,
                                                             const float* __restrict__ sinT,
                                                             const int* __restrict__ pos,
@@ -135,7 +147,8 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(bf16* __restrict__ x
                                                             bf16* __restrict__ vc, long sb, long st, long sh,
                                                             long kcb, long kct, long kch, long vcb, long vct,
                                                             long vch, int B, int T, int H, int Hkv, int hd,
-                                                            int Tmax, bool per_row) {
+                                                            int Tmax, bool per_row,
+                                                            std::conditional_t<PAGED, PagedTable, NoTable> tb) {
   const int vpr = hd / 8;
   const int NH = H + 2 * Hkv;
   const long total = (long)B * T * NH * vpr;
@@ -151,10 +164,17 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(bf16* __restrict__ x
     const long row = (per_row ? index[b] : row0) + t;  // ragged batch: each sequence's own cache row
     if (hh >= H && (row >= Tmax || row < 0)) continue;
     if (hh >= H && !SPA_DBG_OK(row, Tmax)) continue;
+    long cb = b, crow = row;  // cache batch and row of a k / v head
+    if constexpr (PAGED) {
+      cb = 0;
+      if (hh >= H) {  // row is inside [0, NP * page_size): the table index is inside the table
+        crow = paged_pool_row(tb, paged_page(tb, b, row), row);
+      }
+    }
     const bf16* src = x + b * sb + t * st + hh * sh;
     bf16* dst = hh < H ? x + b * sb + t * st + hh * sh
-                       : (hh < H + Hkv ? kc + b * kcb + row * kct + (hh - H) * kch
-                                       : vc + b * vcb + row * vct + (hh - H - Hkv) * vch);
+                       : (hh < H + Hkv ? kc + cb * kcb + crow * kct + (hh - H) * kch
+                                       : vc + cb * vcb + crow * vct + (hh - H - Hkv) * vch);
     float a[8];
     if (hh >= H + Hkv) {  // v: plain copy into the cache
       load8(src + v * 8, a);
@@ -228,7 +248,64 @@ void rope_kv_write_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor
         (bf16*)x.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(),
         index.data_ptr<int64_t>(), (bf16*)kc.data_ptr(), (bf16*)vc.data_ptr(), x.stride(0), x.stride(1),
         x.stride(2), kc.stride(0), kc.stride(1), kc.stride(2), vc.stride(0), vc.stride(1), vc.stride(2), B, T,
-        (int)H, (int)Hkv, hd, (int)kc.size(1), per_row);
+        (int)H, (int)Hkv, hd, (int)kc.size(1), per_row, NoTable{});
+  };
+  if (mode == 0) launch(std::integral_constant<int, 0>{});
+  else launch(std::integral_constant<int, 1>{});
+  SPA_LAUNCH_CHECK();
+}
+
+// rope_kv_write_ into a paged cache: kpool / vpool bf16 [num_pages, page_size, Hkv, hd], block_table
+// int32 [B, NP]. Logical rows outside [0, NP * page_size) are dropped; rows a sequence has not reserved
+// land in the null page.
+void rope_kv_write_paged_(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                          const at::Tensor& index, const at::Tensor& kpool, const at::Tensor& vpool,
+                          const at::Tensor& block_table, int64_t H, int64_t Hkv, int64_t mode, bool per_row) {
+  for (auto* t : {&x, &kpool, &vpool}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 && t->dim() == 4 && t->stride(3) == 1,
+                "rope_kv_write_paged: bf16 x [B, T, heads, hd] and pools [num_pages, page_size, Hkv, hd], contiguous hd");
+    TORCH_CHECK(t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 && t->stride(2) % 8 == 0 &&
+                    (uintptr_t)t->data_ptr() % 16 == 0,
+                "rope_kv_write_paged: 16-byte aligned rows");
+  }
+  const int B = x.size(0), T = x.size(1), hd = x.size(3);
+  TORCH_CHECK(x.size(2) == H + 2 * Hkv && hd % 16 == 0, "rope_kv_write_paged: x must be packed [B, T, H + 2 Hkv, hd]");
+  const int64_t num_pages = kpool.size(0), page = kpool.size(1);
+  TORCH_CHECK(page >= 16 && page <= 256 && (page & (page - 1)) == 0,
+              "rope_kv_write_paged: page_size must be a power of two in [16, 256], got ", page);
+  TORCH_CHECK(vpool.sizes() == kpool.sizes() && kpool.size(2) == Hkv && kpool.size(3) == hd && num_pages >= 1,
+              "rope_kv_write_paged: pool shape mismatch");
+  TORCH_CHECK(kpool.stride(0) == page * kpool.stride(1) && vpool.stride(0) == page * vpool.stride(1),
+              "rope_kv_write_paged: a pool's pages must be back to back (stride(0) == page_size * stride(1))");
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == x.device() && kpool.device() == x.device() &&
+                  vpool.device() == x.device() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+                  block_table.size(0) == B && block_table.is_contiguous(),
+              "rope_kv_write_paged: block_table must be a contiguous int32 [B, NP] tensor on x's device");
+  const int64_t NP = block_table.size(1);
+  TORCH_CHECK(NP * page < (1L << 31) && num_pages * page < (1L << 31), "rope_kv_write_paged: rows must fit an int32");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.is_contiguous() && sin.is_contiguous() && cos.size(1) == hd / 2,
+              "rope_kv_write_paged: fp32 [Tmax, hd/2] tables");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous() && pos.numel() == (int64_t)B * T,
+              "rope_kv_write_paged: pos must be device int32 [B, T]");
+  TORCH_CHECK(index.is_cuda() && index.scalar_type() == at::kLong && index.numel() >= 1,
+              "rope_kv_write_paged: index must be a device int64 tensor");
+  TORCH_CHECK(!per_row || (index.numel() == B && index.is_contiguous()),
+              "rope_kv_write_paged: per_row needs one index per sequence (", B, "), got ", index.numel());
+  TORCH_CHECK(mode == 0 || mode == 1, "rope_kv_write_paged: mode 0 (interleaved) or 1 (rotate_half)");
+  DeviceGuard g(x.device());
+  const long total = (long)B * T * (H + 2 * Hkv) * (hd / 8);
+  if (total == 0) return;
+  const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+  int lg = 0;
+  while ((1 << lg) < page) ++lg;
+  const PagedTable tb{block_table.data_ptr<int>(), (int)NP, lg, (int)num_pages};
+  auto launch = [&](auto modec) {
+    constexpr int M = decltype(modec)::value;
+    rope_kv_write_kernel<M, true><<<grid, 256, 0, stream()>>>(
+        (bf16*)x.data_ptr(), cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(),
+        index.data_ptr<int64_t>(), (bf16*)kpool.data_ptr(), (bf16*)vpool.data_ptr(), x.stride(0), x.stride(1),
+        x.stride(2), 0L, kpool.stride(1), kpool.stride(2), 0L, vpool.stride(1), vpool.stride(2), B, T, (int)H,
+        (int)Hkv, hd, (int)(NP * page), per_row, tb);
   };
   if (mode == 0) launch(std::integral_constant<int, 0>{});
   else launch(std::integral_constant<int, 1>{});
@@ -457,6 +534,8 @@ TORCH_LIBRARY_FRAGMENT(spa, m) {
         "bool inverse) -> ()");
   m.def("rope_kv_write_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kc, "
         "Tensor(c!) vc, int n_heads, int n_kv_heads, int mode=0, bool per_row=False) -> ()");
+  m.def("rope_kv_write_paged_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kpool, "
+        "Tensor(c!) vpool, Tensor block_table, int n_heads, int n_kv_heads, int mode=0, bool per_row=False) -> ()");
   m.def("kv_quant_write_(Tensor k, Tensor v, Tensor(a!) kq, Tensor(b!) ks, Tensor(c!) vq, Tensor(d!) vs, int pos) -> ()");
   m.def("rope_kv_write_q8_(Tensor(a!) x, Tensor cos, Tensor sin, Tensor pos, Tensor index, Tensor(b!) kq, "
         "Tensor(c!) ks, Tensor(d!) vq, Tensor(e!) vs, int n_heads, int n_kv_heads, int mode=0, "
@@ -465,6 +544,7 @@ TORCH_LIBRARY_FRAGMENT(spa, m) {
 TORCH_LIBRARY_IMPL(spa, CUDA, m) {
   m.impl("rope_", &spa::rope_);
   m.impl("rope_kv_write_", &spa::rope_kv_write_);
+  m.impl("rope_kv_write_paged_", &spa::rope_kv_write_paged_);
   m.impl("kv_quant_write_", &spa::kv_quant_write_);
   m.impl("rope_kv_write_q8_", &spa::rope_kv_write_q8_);
 }

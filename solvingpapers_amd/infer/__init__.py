@@ -6,6 +6,9 @@
 * :class:`KVCache` -- preallocated per-layer K/V buffers, written in place; ``quant="fp8"`` (the
   drivers' ``kv_cache="fp8"``, one of :data:`KV_CACHE_FORMATS`) keeps them as e4m3 rows with per-row
   E8M0 scales, one :class:`KV8` handle per layer, read by the fp8 decode-attention kernel;
+* :class:`PagedKVCache` -- the drivers' ``page_size=``: a pool of fixed-size bf16 pages per layer and one
+  block table shared by all layers (one :class:`PagedKV` handle per layer), so memory follows the tokens
+  held; ``reserve`` / ``free`` hand pages out and take them back, :class:`CacheFull` when the pool is short;
 * :func:`generate` -- prompt prefill (flash attention) + token-by-token decode (split-K
   decode kernel, csrc/kernels/decode.hip) with the model's own cache layout, timing
   prefill and decode separately; ``prompt_lens=`` takes a right-padded batch of prompts of different
@@ -18,12 +21,12 @@ Reference entry points (all recompute the whole prefix per token, no cache):
 gpt/gpt-jax.ipynb:821-829, llama3/LLaMA-jax.ipynb:499-511, gemma/gemma.ipynb:608-630,
 deepseekv3/deepseekv3.ipynb:1849-1873.
 """
-from ..ops.attention import KV8
-from .cache import KV_CACHE_FORMATS, KVCache
+from ..ops.attention import KV8, PagedKV
+from .cache import KV_CACHE_FORMATS, CacheFull, KVCache, PagedKVCache
 from .generate import GenerationStats, generate
 from .graph import DecodeState, GraphDecoder, RaggedDecodeState
 from .quant import clear_decode_weights, quantize_decode_weights
 from .sampling import Sampler, sample
 
-__all__ = ["KV8", "KV_CACHE_FORMATS", "KVCache", "DecodeState", "GenerationStats", "GraphDecoder", "RaggedDecodeState",
+__all__ = ["CacheFull", "KV8", "KV_CACHE_FORMATS", "KVCache", "PagedKV", "PagedKVCache", "DecodeState", "GenerationStats", "GraphDecoder", "RaggedDecodeState",
            "Sampler", "clear_decode_weights", "generate", "quantize_decode_weights", "sample"]

@@ -48,8 +48,31 @@ def _sync(t: torch.Tensor):
         torch.cuda.synchronize(t.device)
 
 
+def _new_cache(model, B, total, kv_cache, page_size, num_pages):
+    """The model's cache for ``total`` rows; ``page_size`` / ``num_pages`` only reach models asked for a paged
+    one (their ``new_cache`` names itself in a NotImplementedError when it has none)."""
+    kw = {}
+    if kv_cache is not None:
+        kw["kv_cache"] = kv_cache
+    if page_size is not None or num_pages is not None:
+        kw.update(page_size=page_size, num_pages=num_pages)
+    return model.new_cache(B, total, **kw)
+
+
+def _reserve(cache, rows):
+    """Back ``rows[b]`` rows of every slot of a paged cache before the first launch; all or nothing
+    (CacheFull with no page taken when the pool cannot hold them all)."""
+    from .cache import CacheFull
+    need = sum(cache.pages_for(r) for r in rows)
+    if need > cache.pages_free + cache.pages_used:
+        raise CacheFull(f"{len(rows)} sequences of {list(rows)} rows need {need} pages of {cache.page_size} rows; the "
+                        f"pool holds {cache.num_pages - 1} (plus the null page)")
+    for b, r in enumerate(rows):
+        cache.reserve(b, r)
+
+
 def _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temperature, top_k, top_p, greedy,
-                     eos_token_id, generator, st, timed, sampler, kv_cache):
+                     eos_token_id, generator, st, timed, sampler, kv_cache, page_size=None, num_pages=None):
     """Ragged batch: one right-padded prefill whose logits are gathered at each sequence's last real
     token (causal attention keeps real tokens independent of the pads to their right), then
     ``step_graph`` run eagerly on a RaggedDecodeState positioned at ``prompt_lens``: sequence b writes
@@ -68,7 +91,11 @@ def _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temp
             raise ValueError(f"padded prompts of {T0} tokens exceed the model's context of {limit}")
         total = min(total, limit)
     st.cached = True
-    cache = model.new_cache(B, total) if kv_cache is None else model.new_cache(B, total, kv_cache=kv_cache)
+    cache = _new_cache(model, B, total, kv_cache, page_size, num_pages)
+    if page_size is not None:
+        # each sequence's own rows; the right-padded prefill writes a short one's pad rows past its
+        # reservation into the null page, so padding costs no pages
+        _reserve(cache, [min(n + max_new_tokens, total) for n in lens.tolist()])
     if timed:
         _sync(ids)
     t0 = time.perf_counter()
@@ -109,7 +136,8 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
              top_k: Optional[int] = None, top_p: Optional[float] = None, greedy: bool = False,
              eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              stats: Optional[GenerationStats] = None, timed: bool = False, sampler=None,
-             kv_cache: Optional[str] = None, prompt_lens=None, pad_token_id: int = 0) -> torch.Tensor:
+             kv_cache: Optional[str] = None, prompt_lens=None, pad_token_id: int = 0,
+             page_size: Optional[int] = None, num_pages: Optional[int] = None) -> torch.Tensor:
     """ids [B, T0] -> [B, T0 + n] (n <= max_new_tokens; stops early once every sequence has
     produced ``eos_token_id``, checked every 16 tokens to keep the host out of the loop).
     ``sampler`` (an infer.Sampler) replaces ``sample(...)``: one fused launch per token on the GPU,
@@ -121,7 +149,13 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
     RIGHT-padded (what stands after a row's len_b tokens is ignored), every sequence decodes from
     its own position, and row b of the result holds its prompt, its n new tokens from column len_b,
     then ``pad_token_id`` (also after a row's ``eos_token_id``). Models with ``step_graph`` and a
-    (k, v) cache: LLaMA3 and Gemma."""
+    (k, v) cache: LLaMA3 and Gemma.
+
+    ``page_size`` (a power of two in [16, 256]): decode from a paged KV cache (infer/cache.py
+    PagedKVCache; LLaMA3 and Gemma, bf16 pages) of ``num_pages`` pages per layer (None: enough for every
+    slot's full length). Every sequence's rows are reserved before the first launch -- T0 +
+    max_new_tokens each, or ``prompt_lens[b] + max_new_tokens`` for a ragged batch -- so a pool too
+    small raises ``CacheFull`` with no work done. Pages are not freed when a row reaches EOS."""
     was = model.training
     model.eval()
     timed = timed or stats is not None  # stats requested -> device-synchronised phase timings
@@ -133,14 +167,16 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
     try:
         if prompt_lens is not None:
             out = _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temperature, top_k, top_p,
-                                   greedy, eos_token_id, generator, st, timed, sampler, kv_cache)
+                                   greedy, eos_token_id, generator, st, timed, sampler, kv_cache, page_size, num_pages)
         elif hasattr(model, "new_cache") and hasattr(model, "step"):
             st.cached = True
             total = T0 + max_new_tokens
             if limit is not None:
                 total = min(total, limit)
             prompt = ids[:, -total:] if T0 > total else ids
-            cache = model.new_cache(B, total) if kv_cache is None else model.new_cache(B, total, kv_cache=kv_cache)
+            cache = _new_cache(model, B, total, kv_cache, page_size, num_pages)
+            if page_size is not None:
+                _reserve(cache, [total] * B)
             if timed:
                 _sync(ids)
             t0 = time.perf_counter()
@@ -173,6 +209,9 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
         else:
             if kv_cache not in (None, "bf16"):
                 raise NotImplementedError(f"kv_cache={kv_cache!r} needs a model with the cached-decoding protocol")
+            if page_size is not None or num_pages is not None:
+                raise NotImplementedError(f"page_size needs a model with the cached-decoding protocol; "
+                                          f"{type(model).__name__} has none")
             block = limit or getattr(getattr(model, "c", None), "block_size", None)
             t1 = time.perf_counter()
             for n in range(max_new_tokens):

@@ -22,6 +22,11 @@ tensors hold one entry per sequence (``index`` long [B], ``kv_len`` int32 [B]), 
 entry b for sequence b, so right-padded prompts of different lengths decode together and
 ``prefill_row`` puts a new prompt into one slot while the others continue.
 
+``GraphDecoder(page_size=N)`` decodes from a paged KV cache (infer/cache.py PagedKVCache): the captured
+step writes and reads cache rows through a block table that lives in one static device tensor.
+``reserve`` / ``free`` change it from the host between replays; a replay does no host work, so every row
+a run of replays will write must be reserved before the run.
+
 Protocol a model implements: ``new_cache(B, max_len)``, ``step(ids, cache, pos)`` (eager
 prefill; ``last=`` for a ragged one) and ``step_graph(ids, cache, state)`` (graph-safe decode
 step: no host syncs).
@@ -126,16 +131,26 @@ RAGGED_UNSUPPORTED = ("ragged batches (per-sequence positions) cover the RoPE mo
 
 class GraphDecoder:
     def __init__(self, model, batch: int, max_len: int, greedy: bool = True, warmup: int = 2, sampler=None,
-                 kv_cache: Optional[str] = None, ragged: bool = False):
+                 kv_cache: Optional[str] = None, ragged: bool = False, page_size: Optional[int] = None,
+                 num_pages: Optional[int] = None):
         """``ragged=True`` captures the step over a :class:`RaggedDecodeState`: every sequence at its own
-        position (prompts of different lengths, ``prefill_row`` to refill one slot mid-stream)."""
+        position (prompts of different lengths, ``prefill_row`` to refill one slot mid-stream).
+
+        ``page_size`` (with or without ``ragged``): a paged KV cache of ``num_pages`` pages per layer
+        (None: enough for every slot's ``max_len``). ``prefill`` / ``prefill_row`` / ``generate`` reserve
+        the rows they are about to write; a caller that replays the graph itself reserves with
+        :meth:`reserve` BEFORE the replays -- a replay does no host work, and a row written without a
+        reservation lands in the null page and is lost."""
         self.model, self.batch, self.max_len, self.greedy = model, batch, max_len, greedy
         self.ragged = ragged
         dev = next(model.parameters()).device
         self.sampler = sampler.to(dev) if sampler is not None else None
         # kv_cache="fp8": the captured step quantises its K/V row and attends over e4m3 rows
-        self.cache = model.new_cache(batch, max_len) if kv_cache is None else \
-            model.new_cache(batch, max_len, kv_cache=kv_cache)
+        kw = {} if kv_cache is None else {"kv_cache": kv_cache}
+        if page_size is not None or num_pages is not None:
+            kw.update(page_size=page_size, num_pages=num_pages)
+        self.cache = model.new_cache(batch, max_len, **kw)
+        self.paged = page_size is not None
         self.state = RaggedDecodeState(batch, max_len, dev) if ragged else DecodeState(batch, max_len, dev)
         self.ids = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.logits: Optional[torch.Tensor] = None
@@ -169,36 +184,71 @@ class GraphDecoder:
         if self.sampler is not None:   # the warm-up calls consumed offsets; the stream starts at 0
             self.sampler.offset.zero_()
 
+    # ---------------------------------------------------------------- paged cache
+    def reserve(self, b: int, n_rows: int) -> None:
+        """Back rows [0, n_rows) of slot ``b`` (paged cache): idempotent, only adds pages; ``CacheFull``
+        changes nothing. Whatever the coming replays write must be reserved before them."""
+        self._paged_only("reserve")
+        self.cache.reserve(b, n_rows)
+
+    def free(self, b: int) -> None:
+        """Return slot ``b``'s pages to the pool (paged cache). The slot's position is the caller's: park
+        it with ``state.active[b] = 0`` or refill it with ``prefill_row``."""
+        self._paged_only("free")
+        self.cache.free(b)
+
+    def _paged_only(self, what):
+        if not self.paged:
+            raise ValueError(f"GraphDecoder.{what}: the decoder was built without page_size")
+
+    def _reserve_all(self, rows) -> None:
+        """Free every slot and back ``rows[b]`` rows of each; all or nothing (CacheFull before any change)."""
+        from .cache import CacheFull
+        need = sum(self.cache.pages_for(r) for r in rows)
+        if need > self.cache.num_pages - 1:
+            raise CacheFull(f"{len(rows)} sequences of {list(rows)} rows need {need} pages of "
+                            f"{self.cache.page_size} rows; the pool holds {self.cache.num_pages - 1}")
+        self.cache.free_all()
+        for b, r in enumerate(rows):
+            self.cache.reserve(b, r)
+
     @torch.no_grad()
-    def prefill(self, ids: torch.Tensor, prompt_lens=None) -> torch.Tensor:
+    def prefill(self, ids: torch.Tensor, prompt_lens=None, reserve=None) -> torch.Tensor:
         """Eager prompt pass: fills cache rows [0, T0), positions the state at T0 and returns
         the last position's logits. ``prompt_lens`` (``ragged=True`` only): ``ids`` is right-padded,
         sequence b has ``prompt_lens[b]`` real tokens; its logits are those of its last real token and
         its state is positioned at ``prompt_lens[b]`` (the pad rows the pass wrote into the cache lie
-        beyond kv_len and are overwritten as the sequence grows)."""
+        beyond kv_len and are overwritten as the sequence grows). Paged cache: every slot is freed and
+        each prompt's rows are reserved (``reserve``: that many rows per slot instead, a list, for the
+        tokens to come); a short prompt's pad rows go to the null page."""
         T0 = ids.shape[1]
         if T0 >= self.max_len:
             raise ValueError(f"prompt of {T0} tokens leaves no room in a {self.max_len}-token cache")
+        if prompt_lens is not None and not self.ragged:
+            raise ValueError("GraphDecoder: prompt_lens needs ragged=True (the uniform state holds one position)")
+        lens = None if prompt_lens is None else check_prompt_lens(prompt_lens, self.batch, T0, ids.device)
+        if self.paged:
+            held = [T0] * self.batch if lens is None else lens.tolist()
+            self._reserve_all(held if reserve is None else [max(h, int(r)) for h, r in zip(held, reserve)])
         if self.ragged:
             self.state.active.fill_(1)   # a batch prefill restarts every slot
         if prompt_lens is None:
             lg = self.model.step(ids, self.cache, 0)
             self.state.set(T0)
             return lg
-        if not self.ragged:
-            raise ValueError("GraphDecoder: prompt_lens needs ragged=True (the uniform state holds one position)")
-        lens = check_prompt_lens(prompt_lens, self.batch, T0, ids.device)
         lg = self.model.step(ids, self.cache, 0, last=lens - 1)
         self.state.set(lens)
         return lg
 
     @torch.no_grad()
-    def prefill_row(self, b: int, ids: torch.Tensor) -> torch.Tensor:
+    def prefill_row(self, b: int, ids: torch.Tensor, reserve: Optional[int] = None) -> torch.Tensor:
         """Prefill one sequence (``ids`` 1-D) into slot ``b`` while the other slots keep their cache
         rows and positions (``ragged=True``): the prompt runs through the batch-row views
         ``cache.rows(b, b + 1)`` and ``state.set_row`` positions the slot behind it. Returns the
         prompt's last-position logits [V]; feeding the next token (``self.ids[b]``) and
-        ``state.active[b]`` are the caller's."""
+        ``state.active[b]`` are the caller's. Paged cache: slot ``b`` is freed and ``max(len(ids),
+        reserve)`` rows are reserved for it (``reserve``: the prompt plus the tokens the coming replays
+        will add); ``CacheFull`` leaves the slot as it was."""
         if not self.ragged:
             raise ValueError("GraphDecoder: prefill_row needs ragged=True")
         if not 0 <= b < self.batch:
@@ -207,6 +257,14 @@ class GraphDecoder:
         T = ids.shape[1]
         if not 1 <= T < self.max_len:
             raise ValueError(f"prompt of {T} tokens does not fit a {self.max_len}-token cache")
+        if self.paged:
+            from .cache import CacheFull
+            rows = max(T, int(reserve or 0))
+            if self.cache.pages_for(rows) > self.cache.pages_free + self.cache.held(b):
+                raise CacheFull(f"slot {b} needs {self.cache.pages_for(rows)} pages for {rows} rows; "
+                                f"{self.cache.pages_free} are free and it holds {self.cache.held(b)}")
+            self.cache.free(b)
+            self.cache.reserve(b, rows)
         lg = self.model.step(ids, self.cache.rows(b, b + 1), 0)
         self.state.set_row(b, T)
         return lg[0]
@@ -228,12 +286,16 @@ class GraphDecoder:
         lens = None
         if prompt_lens is not None:
             lens = check_prompt_lens(prompt_lens, self.batch, ids.shape[1], ids.device)
-        lg = self.prefill(ids, lens)
+        # the i-th replay writes cache row len + i of every sequence: the longest prompt sets the room
+        n = min(max_new_tokens, self.max_len - (ids.shape[1] if lens is None else int(lens.max())) + 1)
+        # paged cache: each row's len + n rows are reserved before the replay loop (a pool too small raises
+        # CacheFull here, before the cache or the positions change)
+        held = [ids.shape[1]] * self.batch if lens is None else lens.tolist()
+        lg = self.prefill(ids, lens, reserve=[min(h + n, self.max_len) for h in held]) if self.paged else \
+            self.prefill(ids, lens)
         if stats is not None:
             torch.cuda.synchronize()
         t1 = time.perf_counter()
-        # the i-th replay writes cache row len + i of every sequence: the longest prompt sets the room
-        n = min(max_new_tokens, self.max_len - (ids.shape[1] if lens is None else int(lens.max())) + 1)
         out = torch.empty(self.batch, n, dtype=torch.long, device=ids.device)
         if self.sampler is not None:
             self.sampler(lg, out=self.ids)   # the first token: same kernel, next offset of the stream

@@ -868,8 +868,12 @@ class DeepSeekV3(tnn.Module):
         return c.mtp_lambda * tot / max(1, len(self.mtp_layers))
 
     # ---------------------------------------------------------------- inference
-    def new_cache(self, B, Tmax, kv_cache=None):
+    def new_cache(self, B, Tmax, kv_cache=None, page_size=None, num_pages=None):
         c = self.c
+        if page_size is not None or num_pages is not None:
+            raise NotImplementedError("page_size: the paged KV cache covers the GQA / MQA K/V caches (LLaMA3, Gemma); "
+                                      "DeepSeek-V3 caches MLA latents (one compressed row per token), which it "
+                                      "does not page")
         if kv_cache not in (None, "bf16"):
             raise NotImplementedError(f"kv_cache={kv_cache!r}: the fp8 KV cache covers the GQA / MQA K/V caches; "
                                       "DeepSeek-V3 caches MLA latents (one compressed row per token), which it "

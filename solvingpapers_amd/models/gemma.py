@@ -533,12 +533,13 @@ class Gemma(tnn.Module):
     def max_context(self):
         return self.c.max_seq_len
 
-    def new_cache(self, B, Tmax, kv_cache=None):
-        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py)."""
-        from ..infer.cache import KVCache, kv_cache_quant
+    def new_cache(self, B, Tmax, kv_cache=None, page_size=None, num_pages=None):
+        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales; ``page_size``: a PagedKVCache of bf16
+        pages, ``num_pages`` per layer (infer/cache.py)."""
+        from ..infer.cache import new_kv_cache
         c = self.c
-        return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.embed.device, dtype=self.embed.dtype,
-                       quant=kv_cache_quant(kv_cache))
+        return new_kv_cache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.embed.device,
+                            dtype=self.embed.dtype, kv_cache=kv_cache, page_size=page_size, num_pages=num_pages)
 
     ragged_decode = True   # per-sequence positions (infer.RaggedDecodeState) through step / step_graph
 

@@ -159,9 +159,13 @@ class GPT(tnn.Module):
     def max_context(self):
         return self.c.block_size
 
-    def new_cache(self, B, Tmax, kv_cache=None):
-        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py)."""
+    def new_cache(self, B, Tmax, kv_cache=None, page_size=None, num_pages=None):
+        """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py). The paged cache
+        (``page_size``) is not covered."""
         from ..infer.cache import KVCache, kv_cache_quant
+        if page_size is not None or num_pages is not None:
+            raise NotImplementedError("page_size: the paged KV cache covers the RoPE models with a graph decode "
+                                      "step, LLaMA3 and Gemma; GPT is not covered")
         c = self.c
         return KVCache(c.num_layers, B, Tmax, c.num_heads, c.emb_dim // c.num_heads,
                        device=self.token_embed.device, dtype=self.token_embed.dtype, quant=kv_cache_quant(kv_cache))

@@ -25,7 +25,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from ..infer.cache import KVCache, kv_cache_quant
+from ..infer.cache import new_kv_cache
 from ..infer.graph import DecodeState
 from ..infer.sampling import sample  # noqa: F401  (re-exported: reference-style sampling)
 from ..ops import attention_packed, embedding, linear, linear_cross_entropy, rms_norm, rope_packed_
@@ -247,12 +247,13 @@ class Llama3(nn.Module):
     def max_context(self):
         return self.c.max_seq_len
 
-    def new_cache(self, B, Tmax, kv_cache=None):
+    def new_cache(self, B, Tmax, kv_cache=None, page_size=None, num_pages=None):
         """``kv_cache="fp8"``: e4m3 rows with per-row E8M0 scales (infer/cache.py); None / "bf16": the
-        model-dtype cache."""
+        model-dtype cache. ``page_size``: a PagedKVCache of bf16 pages, ``num_pages`` per layer."""
         c = self.c
-        return KVCache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.tok_embeddings.device,
-                       dtype=self.tok_embeddings.dtype, quant=kv_cache_quant(kv_cache))
+        return new_kv_cache(c.n_layers, B, Tmax, c.n_kv_heads, c.head_dim, device=self.tok_embeddings.device,
+                            dtype=self.tok_embeddings.dtype, kv_cache=kv_cache, page_size=page_size,
+                            num_pages=num_pages)
 
     ragged_decode = True   # per-sequence positions (infer.RaggedDecodeState) through step / step_graph
 

@@ -425,7 +425,7 @@ def _decode_ok(q, k, v):
                and t.data_ptr() % 8 == 0 for t in (q, k, v))
 
 
-def decode_attention(q, k, v, causal=True, scale=None, nsplit=0, kv_len=None, per_row=False):
+def decode_attention(q, k, v=None, causal=True, scale=None, nsplit=0, kv_len=None, per_row=False):
     """Few new query rows against a KV cache: q [B,Tq,H,hd], k/v [B,Tk,Hkv,hd] (cache views,
     the last Tq cache rows are the query tokens). Split-K HIP kernel (csrc/kernels/decode.hip)
     when Tq * H / Hkv <= 16, else the flash kernel. Inference only (no autograd).
@@ -433,7 +433,13 @@ def decode_attention(q, k, v, causal=True, scale=None, nsplit=0, kv_len=None, pe
     ``kv_len`` (device int32 [1]): k/v are whole cache buffers and only the first *kv_len
     rows are valid -- the form a captured hipGraph decode step replays at every position.
     ``per_row`` (ragged batch): ``kv_len`` is int32 [B] and sequence b counts its own first
-    kv_len[b] rows. On the CPU both forms run the pure-torch oracles (ops/reference.py)."""
+    kv_len[b] rows. On the CPU both forms run the pure-torch oracles (ops/reference.py).
+
+    ``k`` a :class:`PagedKV` layer (``v`` None): its ``max_len`` rows, :func:`kv_cache_attend`'s route."""
+    if isinstance(k, PagedKV):
+        if v is not None:
+            raise ValueError("decode_attention: a PagedKV layer holds both pools; pass v=None")
+        return kv_cache_attend(q, k, None, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len, per_row=per_row)
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     if per_row and kv_len is None:
         raise ValueError("decode_attention: per_row needs kv_len (int32 [B])")
@@ -480,6 +486,66 @@ class KV8:
                 reference.dequant_kv8(self.vq[:, :n], self.vs, self.dtype))
 
 
+PAGE_SIZES = (16, 32, 64, 128, 256)
+
+
+def check_page_size(page_size) -> int:
+    """``page_size`` as an int: a power of two in [16, 256] (ValueError otherwise)."""
+    if isinstance(page_size, bool) or not isinstance(page_size, int) or page_size not in PAGE_SIZES:
+        raise ValueError(f"page_size must be a power of two in [16, 256], got {page_size!r}")
+    return page_size
+
+
+class PagedKV:
+    """One layer of a paged KV cache (infer/cache.py ``PagedKVCache``; PagedAttention, Kwon et al., SOSP
+    2023): ``k`` / ``v`` bf16 page pools [num_pages, page_size, Hkv, hd] and ``block_table`` int32 [B, NP]
+    (contiguous, on the pools' device, ONE tensor shared by every layer). Logical row r of sequence b
+    lives at pool row ``block_table[b, r >> lg] * page_size + (r & (page_size - 1))``
+    (reference.paged_rows). Page 0 is the null page: never handed out, every unassigned entry is 0, so a
+    write to an unreserved row lands there and nothing valid reads it."""
+    __slots__ = ("k", "v", "block_table", "page_size", "max_len")
+
+    def __init__(self, k, v, block_table, page_size=None, max_len=None):
+        ps = check_page_size(int(k.shape[1]) if page_size is None else page_size)
+        if k.dim() != 4 or k.shape != v.shape or k.shape[1] != ps:
+            raise ValueError(f"PagedKV: pools must be [num_pages, {ps}, Hkv, hd], got {tuple(k.shape)} / {tuple(v.shape)}")
+        if block_table.dim() != 2 or block_table.dtype != torch.int32 or not block_table.is_contiguous() \
+                or block_table.device != k.device:
+            raise ValueError("PagedKV: block_table must be a contiguous int32 [B, NP] tensor on the pools' device")
+        self.k, self.v, self.block_table, self.page_size = k, v, block_table, ps
+        # the cache length the owner asked for (<= table_rows): what a whole-cache attend passes as Tk, so
+        # the decode kernel cuts the same splits as over a contiguous [B, max_len] cache
+        self.max_len = self.table_rows if max_len is None else int(max_len)
+        if not 0 < self.max_len <= self.table_rows:
+            raise ValueError(f"PagedKV: max_len {max_len} outside the table's {self.table_rows} rows")
+
+    @property
+    def table_rows(self):
+        """Logical rows the table addresses: NP * page_size."""
+        return self.block_table.shape[1] * self.page_size
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.k, self.v))
+
+    def gathered(self, n):
+        """(k, v) rows [0, n) of every sequence as contiguous [B, n, Hkv, hd] tensors (unreserved rows
+        read the null page)."""
+        return (reference.paged_gather(self.k, self.block_table, n),
+                reference.paged_gather(self.v, self.block_table, n))
+
+
+def _decode_paged_ok(q, cache, n):
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4 and q.shape[-1] in FLASH_HD
+            and cache.k.dtype == torch.bfloat16):
+        return False
+    B, Tq, H, hd = q.shape
+    Hkv = cache.k.shape[2]
+    if H % Hkv or Tq * (H // Hkv) > DECODE_MAX_ROWS or Tq > n:
+        return False
+    return (q.stride(3) == 1 and q.stride(0) % 4 == 0 and q.stride(1) % 4 == 0 and q.stride(2) % 4 == 0
+            and q.data_ptr() % 8 == 0)
+
+
 def _kv8_write_ok(k, v):
     hd = k.shape[-1]
     return (k.is_cuda and k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16 and 8 <= hd <= 512
@@ -493,6 +559,17 @@ def kv_cache_write(cache, k, v, pos):
     ``(kc, vc)`` pair (two slice copies, as the models always did) or a :class:`KV8` layer (bf16 on
     the GPU: the quantising kv_quant_write_ kernel, one launch for both; else the torch formula)."""
     T = k.shape[1]
+    if isinstance(cache, PagedKV):
+        # a :class:`PagedKV` layer: T rows per sequence scattered through the block table (index_copy_ on
+        # the flattened pools; the prefill is GEMM-bound, this is not the hot path). Rows a sequence has
+        # not reserved (the pad rows of a right-padded prefill) land in the null page.
+        if pos < 0 or pos + T > cache.table_rows:
+            raise ValueError(f"KV cache overflow: rows [{pos}, {pos + T}) of {cache.table_rows}")
+        rows = reference.paged_rows(cache.block_table, torch.arange(pos, pos + T, device=k.device),
+                                    cache.page_size).reshape(-1)
+        for x, pool in ((k, cache.k), (v, cache.v)):
+            pool.view(-1, *pool.shape[2:]).index_copy_(0, rows, x.reshape(-1, *x.shape[2:]).to(pool.dtype))
+        return
     if not isinstance(cache, KV8):
         kc, vc = cache
         kc[:, pos:pos + T] = k
@@ -517,6 +594,9 @@ def rope_kv_cache_write_(cache, x4, cos, sin, positions, index, n_heads, n_kv_he
     pure-torch oracle (reference.rope_kv_write)."""
     if not x4.is_cuda:
         reference.rope_kv_write(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mode, per_row)
+    elif isinstance(cache, PagedKV):
+        _ext.ops().rope_kv_write_paged_(x4, cos, sin, positions, index, cache.k, cache.v, cache.block_table,
+                                        n_heads, n_kv_heads, mode, per_row)
     elif isinstance(cache, KV8):
         _ext.ops().rope_kv_write_q8_(x4, cos, sin, positions, index, cache.kq, cache.ks, cache.vq, cache.vs,
                                      n_heads, n_kv_heads, mode, per_row)
@@ -545,7 +625,27 @@ def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=
     prompt prefill at position 0) is attended directly; else attn_decode_q8 over the e4m3 rows when the
     decode kernel applies (Tq * H / Hkv <= 16, hd 64 / 128 / 256, bf16 q on the GPU); else rows [0, n)
     are dequantised and take :func:`decode_attention`'s route (``kv_len`` applies there only on the
-    CPU, through the oracle). ``per_row``: ``kv_len`` is int32 [B], one length per sequence."""
+    CPU, through the oracle). ``per_row``: ``kv_len`` is int32 [B], one length per sequence.
+
+    A :class:`PagedKV` layer (``n`` None: its ``max_len`` rows): ``fresh`` as above; else
+    attn_decode_paged through the block table when the decode kernel applies; else rows [0, n) are
+    gathered into a contiguous [B, n, Hkv, hd] pair that takes :func:`decode_attention`'s route."""
+    if isinstance(cache, PagedKV):
+        if per_row and kv_len is None:
+            raise ValueError("kv_cache_attend: per_row needs kv_len (int32 [B])")
+        if fresh is not None:
+            return decode_attention(q, fresh[0], fresh[1], causal=causal, scale=scale, nsplit=nsplit)
+        rows = cache.max_len if n is None else n
+        if rows > cache.table_rows:
+            raise ValueError(f"kv_cache_attend: {rows} rows outside the block table's {cache.table_rows}")
+        if _decode_paged_ok(q, cache, rows):
+            sc = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+            return _ext.ops().attn_decode_paged(q, cache.k, cache.v, cache.block_table, sc, causal, int(nsplit),
+                                                int(rows), kv_len, per_row)[0]
+        if kv_len is not None and q.is_cuda:
+            raise ValueError("kv_cache_attend: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
+        k, v = cache.gathered(rows)
+        return decode_attention(q, k, v, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len, per_row=per_row)
     if not isinstance(cache, KV8):
         kc, vc = cache
         if n is not None:

@@ -310,13 +310,56 @@ def attention_per_row(q, k, v, kv_len, causal=True, scale=None):
     return torch.cat([o for o, _ in parts]), torch.cat([l for _, l in parts])
 
 
+def paged_rows(block_table, rows, page_size):
+    """Pool row ids of a paged KV cache: logical row r of sequence b lives at pool row
+    ``block_table[b, r >> lg] * page_size + (r & (page_size - 1))`` (page_size = 1 << lg).
+    block_table int [B, NP]; rows int [T] (the same rows for every sequence) or [B, T], every one inside
+    [0, NP * page_size). Returns int64 [B, T]."""
+    lg = int(page_size).bit_length() - 1
+    if page_size != 1 << lg:
+        raise ValueError(f"paged_rows: page_size must be a power of two, got {page_size}")
+    bt = block_table.long()
+    r = torch.as_tensor(rows, device=bt.device).long()
+    if r.dim() == 1:
+        r = r[None].expand(bt.shape[0], -1)
+    if not r.is_cuda and r.numel() and (int(r.min()) < 0 or int(r.max()) >= bt.shape[1] * page_size):  # no device sync
+        raise IndexError(f"paged_rows: rows outside the table's [0, {bt.shape[1] * page_size})")
+    return bt.gather(1, r >> lg) * page_size + (r & (page_size - 1))
+
+
+def paged_gather(pool, block_table, n):
+    """Rows [0, n) of every sequence of a paged KV pool, as the contiguous cache would hold them: pool
+    [num_pages, page_size, Hkv, hd], block_table [B, NP] -> [B, n, Hkv, hd]. This is the definition of
+    the paged layout (unreserved rows read the null page, page 0)."""
+    P, ps = pool.shape[0], pool.shape[1]
+    idx = paged_rows(block_table, torch.arange(n, device=pool.device), ps)
+    return pool.reshape(P * ps, *pool.shape[2:])[idx]
+
+
+def attention_paged(q, cache, n, kv_len=None, per_row=False, causal=True, scale=None):
+    """Decode attention over a paged cache layer (``cache.k`` / ``cache.v`` pools, ``cache.block_table``;
+    csrc/kernels/decode.hip attn_decode_paged): :func:`attention` / :func:`attention_per_row` on
+    :func:`paged_gather` of rows [0, n). Returns (out, lse)."""
+    k = paged_gather(cache.k, cache.block_table, n)
+    v = paged_gather(cache.v, cache.block_table, n)
+    if per_row:
+        return attention_per_row(q, k, v, kv_len, causal, scale)
+    if kv_len is not None:
+        n = min(int(torch.as_tensor(kv_len).reshape(-1)[0]), n)
+    return attention(q, k[:, :n], v[:, :n], causal, scale)
+
+
 def rope_kv_write(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mode=0, per_row=False):
     """Decode-step prologue (csrc/kernels/rope.hip rope_kv_write_ / rope_kv_write_q8_) on a packed qkv
     buffer x4 [B, T, H + 2 Hkv, hd]: RoPE at ``positions`` [B, T] on the q heads (in place) and on
     the k heads (mode 0 interleaved, 1 rotate_half); k / v rows into ``cache`` at row index + t
     (``per_row``: index[b] + t). ``cache`` is a (kc, vc) pair [B, Tmax, Hkv, hd] or a KV8-like object
     (kq / ks / vq / vs), which stores :func:`quant_kv8` of the value the pair would hold. Rows
-    outside [0, Tmax) are dropped."""
+    outside [0, Tmax) are dropped. A paged layer (``k`` / ``v`` pools and ``block_table``;
+    rope_kv_write_paged_) takes the same rows through :func:`paged_rows`, Tmax being the table's
+    NP * page_size."""
+    if hasattr(cache, "block_table"):
+        return _rope_kv_write_paged(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mode, per_row)
     B, T = x4.shape[0], x4.shape[1]
     H, KV = n_heads, n_kv_heads
     pos = positions.reshape(B, T)
@@ -346,6 +389,32 @@ def rope_kv_write(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mo
             else:
                 cache[0][b, r] = k[b, t]
                 cache[1][b, r] = v[b, t]
+
+
+def _rope_kv_write_paged(x4, cos, sin, positions, index, cache, n_heads, n_kv_heads, mode, per_row):
+    """:func:`rope_kv_write` into a paged layer: the same rotation, each kept row through
+    :func:`paged_rows` into the flattened pools."""
+    B, T = x4.shape[0], x4.shape[1]
+    H, KV = n_heads, n_kv_heads
+    pos = positions.reshape(B, T)
+    x4[:, :, :H] = rope(x4[:, :, :H], cos, sin, interleaved=mode == 0, positions=pos)
+    k = rope(x4[:, :, H:H + KV], cos, sin, interleaved=mode == 0, positions=pos)
+    v = x4[:, :, H + KV:]
+    idx = [int(i) for i in index.reshape(-1).tolist()]
+    if per_row and len(idx) != B:
+        raise ValueError(f"rope_kv_write: per_row needs {B} indices, got {len(idx)}")
+    rows = idx if per_row else [idx[0]] * B
+    ps = cache.k.shape[1]
+    Tmax = cache.block_table.shape[1] * ps
+    kf, vf = cache.k.view(-1, *cache.k.shape[2:]), cache.v.view(-1, *cache.v.shape[2:])
+    for b in range(B):
+        for t in range(T):
+            r = rows[b] + t
+            if not 0 <= r < Tmax:    # dropped before the table is read
+                continue
+            pr = int(paged_rows(cache.block_table[b:b + 1], [r], ps)[0, 0])
+            kf[pr] = k[b, t]
+            vf[pr] = v[b, t]
 
 
 def gather_rows(x, idx):

@@ -8,7 +8,9 @@ against the bf16 kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 an
 just the token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
 ``--only decode_attn`` runs just the decode-attention rows: attn_decode_q8 over an fp8 KV cache against
 attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes, then
-the per_row (ragged batch) form of both kernels at batch 16: equal lengths and lengths spread 1:4.
+the per_row (ragged batch) form of both kernels at batch 16: equal lengths and lengths spread 1:4, then
+attn_decode_paged (paged KV cache, 16- and 64-row pages in shuffled order) against attn_decode on the same
+rows (``--only decode_attn_paged``: those rows alone).
 """
 import argparse
 import json
@@ -260,6 +262,58 @@ def decode_attn_per_row_rows(iters, rounds=3):
             del ringc, arms
 
 
+def decode_attn_paged_rows(iters, rounds=3):
+    """attn_decode_paged (paged KV cache, pages of 16 and of 64 rows assigned in shuffled order) next to
+    attn_decode on the same rows in a contiguous cache, at DECODE_ATTN_SHAPES, one new token per sequence.
+    Ring of caches (every arm its own, each larger than the last-level cache), A B C C B A order and
+    medians as in decode_attn_rows; all three arms read a device kv_len. ``time_vs_contiguous`` > 1: paging
+    is slower."""
+    ops = _ext.ops()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for H, Hkv, hd, B, Tk in DECODE_ATTN_SHAPES:
+        nbytes = 2 * B * Tk * Hkv * hd * 2
+        ring = max(4, -(-(640 << 20) // nbytes))
+        q = torch.randn(B, 1, H, hd, device=DEV, dtype=BF, generator=g)
+        k, v = (torch.randn(B, Tk, Hkv, hd, device=DEV, dtype=BF, generator=g) for _ in range(2))
+        sc = hd ** -0.5
+        kv_len = torch.tensor([Tk], device=DEV, dtype=torch.int32)
+        rings = {"contiguous": [(k.clone(), v.clone()) for _ in range(ring)]}
+        for page in (16, 64):
+            NP = Tk // page
+            pools = []
+            for i in range(ring):      # every sequence's pages scattered over the pool; page 0 stays the null page
+                perm = torch.randperm(B * NP, generator=torch.Generator().manual_seed(page + i)) + 1
+                bt = perm.view(B, NP).to(DEV, torch.int32)
+                kp, vp = (torch.zeros(B * NP + 1, page, Hkv, hd, device=DEV, dtype=BF) for _ in range(2))
+                idx = bt.long().flatten()
+                kp[idx] = k.view(B * NP, page, Hkv, hd)
+                vp[idx] = v.view(B * NP, page, Hkv, hd)
+                pools.append((kp, vp, bt))
+            rings[f"page{page}"] = pools
+        o0 = ops.attn_decode(q, k, v, sc, True, 0, kv_len)[0]
+        for page in (16, 64):          # the same bits through the table, before anything is timed
+            kp, vp, bt = rings[f"page{page}"][0]
+            assert torch.equal(ops.attn_decode_paged(q, kp, vp, bt, sc, True, 0, Tk, kv_len)[0], o0)
+        arms = {"contiguous": _graphed(lambda: [ops.attn_decode(q, ki, vi, sc, True, 0, kv_len)
+                                                for ki, vi in rings["contiguous"]])}
+        for page in (16, 64):
+            arms[f"page{page}"] = _graphed(lambda page=page: [ops.attn_decode_paged(q, kp, vp, bt, sc, True, 0, Tk, kv_len)
+                                                              for kp, vp, bt in rings[f"page{page}"]])
+        ms = {a: [] for a in arms}
+        for _ in range(rounds):
+            for arm in ("contiguous", "page16", "page64", "page64", "page16", "contiguous"):
+                ms[arm].append(timed(arms[arm], iters) / ring)
+        med = {a: sorted(t)[len(t) // 2] for a, t in ms.items()}
+        for a in arms:
+            name = "attn_decode" if a == "contiguous" else f"attn_decode_paged_{a}"
+            print(json.dumps({"kernel": f"{name}_B{B}_Tk{Tk}_H{H}kv{Hkv}_hd{hd}", "ms": round(med[a], 5),
+                              "GB": round(nbytes / 1e9, 4), "kv_GB_per_s": round(nbytes / med[a] / 1e6, 1),
+                              "min_ms": round(min(ms[a]), 5), "max_ms": round(max(ms[a]), 5), "ring": ring,
+                              **({"time_vs_contiguous": round(med[a] / med["contiguous"], 3)}
+                                 if a != "contiguous" else {})}), flush=True)
+        del rings, arms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -274,7 +328,10 @@ def main():
     if not only or "decode_attn" in only:
         decode_attn_rows(a.iters)
         decode_attn_per_row_rows(a.iters)
-    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn"} else cases()).items():
+    if not only or only & {"decode_attn", "decode_attn_paged"}:
+        decode_attn_paged_rows(a.iters)
+    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn", "decode_attn_paged"}
+                               else cases()).items():
         if only and name not in only:
             continue
         ms = timed(fn, a.iters)
