@@ -13,7 +13,10 @@ decodes with attn_decode_q8 -- the cache's size is reported as ``kv_cache_bytes`
 prompt length per sequence, right-padded; per-sequence positions: GraphDecoder(ragged=True) with ``--graph``) and
 adds ``prompt_lens`` to the result line. ``--page-size N`` decodes from a paged KV cache (infer/cache.py PagedKVCache,
 bf16 pages of N rows) of ``--pages N`` pages per layer (default: enough for every slot's prompt + new rows);
-``kv_cache_bytes`` is then the pools' size. The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
+``kv_cache_bytes`` is then the pools' size. ``--prefill-chunk N`` (with ``--prompt-lens``) runs the prompts in blocks
+of N columns, every block after the first as a multi-token step behind the cached rows (model.extend), and adds
+``prefill_chunk``, ``prefill_s`` and ``peak_mem_bytes`` (torch.cuda.max_memory_allocated over the timed call) to the
+result line; ``--prefill-chunk 0`` reports the same fields for the one-pass prefill. The reference decodes by re-running the whole prefix per token (llama3/LLaMA-jax.ipynb:1629: 20 tokens in 60.6 s on a T4)."""
 from __future__ import annotations
 
 import argparse
@@ -79,7 +82,12 @@ def main(argv=None):
     ap.add_argument("--pages", type=int, default=None,
                     help="pages per layer of the paged cache, the null page included (default: batch * pages per "
                          "sequence + 1)")
+    ap.add_argument("--prefill-chunk", type=int, default=None,
+                    help="ragged batches (--prompt-lens): prefill in blocks of N columns (model.extend behind the "
+                         "first); 0: one pass, but report prefill_s and peak_mem_bytes as the chunked run does")
     a = ap.parse_args(argv)
+    if a.prefill_chunk is not None and a.prompt_lens is None:
+        ap.error("--prefill-chunk needs --prompt-lens (a ragged batch)")
     if a.pages is not None and a.page_size is None:
         ap.error("--pages needs --page-size")
     pkw = {} if a.page_size is None else {"page_size": a.page_size, "num_pages": a.pages}
@@ -106,6 +114,8 @@ def main(argv=None):
     kw = {} if a.sampler != "eager" else {"temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
                                           "generator": torch.Generator(device="cuda").manual_seed(a.seed)}
     rkw = {} if lens is None else {"prompt_lens": lens}    # {}: every call as before the option existed
+    if a.prefill_chunk:
+        rkw["prefill_chunk"] = a.prefill_chunk
     wkw = {} if lens is None else {"prompt_lens": [min(n, 64) for n in lens]}
     if a.sampler != "greedy":
         extra.update(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)
@@ -119,13 +129,15 @@ def main(argv=None):
         dec.generate(ids[:, :64], 4, **kw, **wkw)  # warm-up of the eager prefill path
         if sampler is not None:
             sampler.reseed(a.seed)
+        torch.cuda.reset_peak_memory_stats()
         out = dec.generate(ids, a.new, stats=st, **kw, **rkw)
     else:
         kw = dict(kw, greedy=a.sampler == "greedy", sampler=sampler, **ckw)
         gen = m.generate
-        if pkw:    # the models' generate() carries no paging arguments: the driver itself
+        if pkw or a.prefill_chunk:   # the models' generate() carries no paging or chunking arguments: the driver itself
             from solvingpapers_amd.infer import generate
             gen = lambda *args, **k: generate(m, *args, **k, **pkw)
+        if pkw:
             pool = m.new_cache(a.batch, a.prompt + a.new, **ckw, **pkw)   # what generate() allocates
             cache_bytes = pool.nbytes()
             extra.update(num_pages=pool.num_pages)
@@ -136,8 +148,12 @@ def main(argv=None):
         gen(ids[:, :64], 4, **kw, **wkw)         # warm-up (kernels, allocator)
         if sampler is not None:
             sampler.reseed(a.seed)
+        torch.cuda.reset_peak_memory_stats()
         out = gen(ids, a.new, stats=st, **kw, **rkw)
     torch.cuda.synchronize()
+    if a.prefill_chunk is not None:
+        extra.update(prefill_chunk=a.prefill_chunk, prefill_s=round(st.prefill_s, 4),
+                     peak_mem_bytes=torch.cuda.max_memory_allocated())
     print(json.dumps({"metric": "decode tokens/s", "model": a.model, "graph": a.graph, "batch": a.batch, "prompt": a.prompt,
                       "new_tokens": st.new_tokens, "prefill_tok_s": round(st.prefill_tok_s, 1),
                       "decode_tok_s": round(st.decode_tok_s, 2),

@@ -13,6 +13,9 @@
   decode kernel, csrc/kernels/decode.hip) with the model's own cache layout, timing
   prefill and decode separately; ``prompt_lens=`` takes a right-padded batch of prompts of different
   lengths (ragged batch: per-sequence positions in :class:`RaggedDecodeState`; LLaMA3 and Gemma);
+  ``prefill_chunk=`` runs such prompts in blocks of columns, every block after the first as a multi-token
+  step behind the rows already cached (:class:`ExtendState`, ``model.extend``, the extend-attention
+  kernel csrc/kernels/attention_extend.hip); ``GraphDecoder.extend_row`` appends to one live slot;
 * :func:`quantize_decode_weights` / :func:`clear_decode_weights` -- fp8 weight-only decode:
   block-scaled e4m3 images of the projection matrices, read by the decode GEMV kernels
   (csrc/kernels/gemv.hip); see infer/quant.py.
@@ -24,9 +27,9 @@ deepseekv3/deepseekv3.ipynb:1849-1873.
 from ..ops.attention import KV8, PagedKV
 from .cache import KV_CACHE_FORMATS, CacheFull, KVCache, PagedKVCache
 from .generate import GenerationStats, generate
-from .graph import DecodeState, GraphDecoder, RaggedDecodeState
+from .graph import DecodeState, ExtendState, GraphDecoder, RaggedDecodeState
 from .quant import clear_decode_weights, quantize_decode_weights
 from .sampling import Sampler, sample
 
-__all__ = ["CacheFull", "KV8", "KV_CACHE_FORMATS", "KVCache", "PagedKV", "PagedKVCache", "DecodeState", "GenerationStats", "GraphDecoder", "RaggedDecodeState",
+__all__ = ["CacheFull", "KV8", "KV_CACHE_FORMATS", "KVCache", "PagedKV", "PagedKVCache", "DecodeState", "ExtendState", "GenerationStats", "GraphDecoder", "RaggedDecodeState",
            "Sampler", "clear_decode_weights", "generate", "quantize_decode_weights", "sample"]

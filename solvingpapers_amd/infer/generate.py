@@ -72,15 +72,21 @@ def _reserve(cache, rows):
 
 
 def _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temperature, top_k, top_p, greedy,
-                     eos_token_id, generator, st, timed, sampler, kv_cache, page_size=None, num_pages=None):
+                     eos_token_id, generator, st, timed, sampler, kv_cache, page_size=None, num_pages=None,
+                     prefill_chunk=None):
     """Ragged batch: one right-padded prefill whose logits are gathered at each sequence's last real
     token (causal attention keeps real tokens independent of the pads to their right), then
     ``step_graph`` run eagerly on a RaggedDecodeState positioned at ``prompt_lens``: sequence b writes
     cache row len_b + i at step i (over the pad rows the prefill left there) and attends over its own
     kv_len[b] rows."""
-    from .graph import RAGGED_UNSUPPORTED, RaggedDecodeState, check_prompt_lens, ragged_layout
+    from .graph import (EXTEND_UNSUPPORTED, RAGGED_UNSUPPORTED, RaggedDecodeState, check_chunk, check_prompt_lens,
+                        chunked_prefill, ragged_layout)
     if not getattr(model, "ragged_decode", False):
         raise NotImplementedError(RAGGED_UNSUPPORTED.format(type(model).__name__))
+    if prefill_chunk is not None:
+        check_chunk(prefill_chunk)
+        if not hasattr(model, "extend"):
+            raise NotImplementedError(EXTEND_UNSUPPORTED.format(type(model).__name__))
     B, T0 = ids.shape
     lens = check_prompt_lens(prompt_lens, B, T0, ids.device)
     longest = int(lens.max())
@@ -99,7 +105,10 @@ def _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temp
     if timed:
         _sync(ids)
     t0 = time.perf_counter()
-    logits = model.step(ids, cache, 0, last=lens - 1)
+    if prefill_chunk is not None:
+        logits = chunked_prefill(model, cache, ids, lens, prefill_chunk)
+    else:
+        logits = model.step(ids, cache, 0, last=lens - 1)
     state = RaggedDecodeState(B, total, ids.device)
     state.set(lens)
     if timed:
@@ -137,7 +146,8 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
              eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              stats: Optional[GenerationStats] = None, timed: bool = False, sampler=None,
              kv_cache: Optional[str] = None, prompt_lens=None, pad_token_id: int = 0,
-             page_size: Optional[int] = None, num_pages: Optional[int] = None) -> torch.Tensor:
+             page_size: Optional[int] = None, num_pages: Optional[int] = None,
+             prefill_chunk: Optional[int] = None) -> torch.Tensor:
     """ids [B, T0] -> [B, T0 + n] (n <= max_new_tokens; stops early once every sequence has
     produced ``eos_token_id``, checked every 16 tokens to keep the host out of the loop).
     ``sampler`` (an infer.Sampler) replaces ``sample(...)``: one fused launch per token on the GPU,
@@ -155,7 +165,14 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
     PagedKVCache; LLaMA3 and Gemma, bf16 pages) of ``num_pages`` pages per layer (None: enough for every
     slot's full length). Every sequence's rows are reserved before the first launch -- T0 +
     max_new_tokens each, or ``prompt_lens[b] + max_new_tokens`` for a ragged batch -- so a pool too
-    small raises ``CacheFull`` with no work done. Pages are not freed when a row reaches EOS."""
+    small raises ``CacheFull`` with no work done. Pages are not freed when a row reaches EOS.
+
+    ``prefill_chunk=C`` (ragged batches only): the prompts run in blocks of C columns, every block after
+    the first as a multi-token step behind the rows already cached (``model.extend``; LLaMA3 and Gemma),
+    which bounds the prefill's activation memory. None: one pass."""
+    if prefill_chunk is not None and prompt_lens is None:
+        raise ValueError("generate: prefill_chunk needs prompt_lens (a ragged batch); a uniform batch prefills in "
+                         "one pass")
     was = model.training
     model.eval()
     timed = timed or stats is not None  # stats requested -> device-synchronised phase timings
@@ -167,7 +184,8 @@ def generate(model, ids: torch.Tensor, max_new_tokens: int, temperature: float =
     try:
         if prompt_lens is not None:
             out = _generate_ragged(model, ids, prompt_lens, pad_token_id, max_new_tokens, temperature, top_k, top_p,
-                                   greedy, eos_token_id, generator, st, timed, sampler, kv_cache, page_size, num_pages)
+                                   greedy, eos_token_id, generator, st, timed, sampler, kv_cache, page_size, num_pages,
+                                   prefill_chunk)
         elif hasattr(model, "new_cache") and hasattr(model, "step"):
             st.cached = True
             total = T0 + max_new_tokens

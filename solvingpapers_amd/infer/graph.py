@@ -105,6 +105,90 @@ class RaggedDecodeState(DecodeState):
         self.kv_len.add_(self.active)
 
 
+class ExtendState(RaggedDecodeState):
+    """A :class:`RaggedDecodeState` for ONE multi-token step (``model.extend``): sequence b's ``T`` tokens
+    take cache rows [starts[b], starts[b] + T). ``index`` long [B] = starts, ``positions`` int32 [B, T] =
+    starts[:, None] + arange(T), ``kv_len`` int32 [B] = starts + T. ``starts`` (host list or tensor) is
+    checked on the host: 0 <= starts[b] and starts[b] + T <= max_len, so kv_len[b] never exceeds the
+    cache's rows and every token sits at the position stated."""
+
+    def __init__(self, starts, T: int, max_len: int, device):
+        s = torch.as_tensor(starts).reshape(-1).long().cpu()
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"ExtendState: a step of {T} tokens")
+        if s.numel() < 1:
+            raise ValueError("ExtendState: starts is empty")
+        if int(s.min()) < 0 or int(s.max()) + T > max_len:
+            raise ValueError(f"ExtendState: rows [start, start + {T}) must lie in [0, {max_len}], got starts "
+                             f"{s.tolist()}")
+        self.batch, self.max_len, self.T = s.numel(), max_len, T
+        self.index = s.to(device)
+        self.positions = (self.index[:, None] + torch.arange(T, device=device)[None]).int()
+        self.kv_len = (self.index + T).int()
+        self.active = torch.ones(self.batch, dtype=torch.int32, device=device)
+
+
+EXTEND_UNSUPPORTED = ("multi-token steps behind a live cache (extend, extend_row, chunked prefill) cover LLaMA3 and "
+                      "Gemma; {} has no extend()")
+
+
+def _need_extend(model):
+    if not hasattr(model, "extend"):
+        raise NotImplementedError(EXTEND_UNSUPPORTED.format(type(model).__name__))
+
+
+def check_chunk(chunk) -> int:
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"chunk must be a positive int, got {chunk!r}")
+    return chunk
+
+
+def chunked_prefill(model, cache, ids: torch.Tensor, lens: torch.Tensor, chunk: int) -> torch.Tensor:
+    """Right-padded prompts ``ids`` [B, T0] (``lens`` long [B] real tokens each) into rows [0, T0) of
+    ``cache`` in blocks of ``chunk`` columns: the first through ``model.step`` at position 0, each later
+    one through ``model.extend`` at ``starts = [chunk * i] * B``. Returns logits [B, V], sequence b's
+    taken from the chunk that holds its last real token; chunks wholly past every length are skipped."""
+    chunk = check_chunk(chunk)
+    _need_extend(model)
+    B, T0 = ids.shape
+    out = None
+    for c0 in range(0, int(lens.max()), chunk):
+        c1 = min(c0 + chunk, T0)
+        last = (lens - 1 - c0).clamp(0, c1 - c0 - 1)
+        if c0 == 0:
+            lg = model.step(ids[:, :c1], cache, 0, last=last)
+        else:
+            lg = model.extend(ids[:, c0:c1], cache, [c0] * B, last=last)
+        here = (lens > c0) & (lens <= c1)
+        out = lg if out is None else torch.where(here[:, None], lg, out)
+    return out
+
+
+def extend_row(model, cache, state, b: int, ids: torch.Tensor, reserve: Optional[int] = None) -> torch.Tensor:
+    """Append ``ids`` (1-D) behind slot ``b``'s current position (read on the host from ``state.index[b]``,
+    a synchronisation) through the batch-row views ``cache.rows(b, b + 1)`` and ``model.extend``, then
+    position the slot behind them; the other slots keep their rows and positions. Returns the logits [V]
+    of the last appended token. Paged cache: ``max(pos + len(ids), reserve)`` rows are reserved first
+    (only ever adds pages); ``CacheFull`` is raised before anything changes."""
+    if not getattr(state, "per_row", False):
+        raise ValueError("extend_row needs per-sequence positions (GraphDecoder(ragged=True)): the uniform state "
+                         "holds one position")
+    _need_extend(model)
+    if not 0 <= b < state.batch:
+        raise IndexError(f"slot {b} of {state.batch}")
+    ids = ids.reshape(1, -1)
+    T = ids.shape[1]
+    pos = int(state.index[b])
+    if T < 1 or pos + T >= state.max_len:
+        raise ValueError(f"{T} tokens behind position {pos} do not fit a {state.max_len}-token cache")
+    if hasattr(cache, "block_table"):
+        cache.reserve(b, max(pos + T, int(reserve or 0)))
+    lg = model.extend(ids, cache.rows(b, b + 1), [pos])
+    state.set_row(b, pos + T)
+    return lg[0]
+
+
 def ragged_layout(ids: torch.Tensor, lens: torch.Tensor, new: torch.Tensor, pad_token_id: int) -> torch.Tensor:
     """[B, T0 + n]: row b = its prompt ids[b, :lens[b]], its n new tokens from column lens[b], then
     ``pad_token_id`` (the output layout of ragged generation)."""
@@ -213,15 +297,25 @@ class GraphDecoder:
             self.cache.reserve(b, r)
 
     @torch.no_grad()
-    def prefill(self, ids: torch.Tensor, prompt_lens=None, reserve=None) -> torch.Tensor:
+    def prefill(self, ids: torch.Tensor, prompt_lens=None, reserve=None, chunk: Optional[int] = None) -> torch.Tensor:
         """Eager prompt pass: fills cache rows [0, T0), positions the state at T0 and returns
         the last position's logits. ``prompt_lens`` (``ragged=True`` only): ``ids`` is right-padded,
         sequence b has ``prompt_lens[b]`` real tokens; its logits are those of its last real token and
         its state is positioned at ``prompt_lens[b]`` (the pad rows the pass wrote into the cache lie
         beyond kv_len and are overwritten as the sequence grows). Paged cache: every slot is freed and
         each prompt's rows are reserved (``reserve``: that many rows per slot instead, a list, for the
-        tokens to come); a short prompt's pad rows go to the null page."""
+        tokens to come); a short prompt's pad rows go to the null page.
+
+        ``chunk=C`` (with ``prompt_lens``): the prompt runs in blocks of C columns, the first at position
+        0 as without it, each later one through ``model.extend`` (:func:`chunked_prefill`), which bounds
+        the activation memory of a long prompt. None: one pass."""
         T0 = ids.shape[1]
+        if chunk is not None:
+            check_chunk(chunk)
+            if prompt_lens is None:
+                raise ValueError("GraphDecoder.prefill: chunk needs prompt_lens (and ragged=True): a chunk behind the "
+                                 "first is a per-sequence multi-token step")
+            _need_extend(self.model)
         if T0 >= self.max_len:
             raise ValueError(f"prompt of {T0} tokens leaves no room in a {self.max_len}-token cache")
         if prompt_lens is not None and not self.ragged:
@@ -236,21 +330,28 @@ class GraphDecoder:
             lg = self.model.step(ids, self.cache, 0)
             self.state.set(T0)
             return lg
-        lg = self.model.step(ids, self.cache, 0, last=lens - 1)
+        if chunk is not None:
+            lg = chunked_prefill(self.model, self.cache, ids, lens, chunk)
+        else:
+            lg = self.model.step(ids, self.cache, 0, last=lens - 1)
         self.state.set(lens)
         return lg
 
     @torch.no_grad()
-    def prefill_row(self, b: int, ids: torch.Tensor, reserve: Optional[int] = None) -> torch.Tensor:
+    def prefill_row(self, b: int, ids: torch.Tensor, reserve: Optional[int] = None,
+                    chunk: Optional[int] = None) -> torch.Tensor:
         """Prefill one sequence (``ids`` 1-D) into slot ``b`` while the other slots keep their cache
         rows and positions (``ragged=True``): the prompt runs through the batch-row views
         ``cache.rows(b, b + 1)`` and ``state.set_row`` positions the slot behind it. Returns the
         prompt's last-position logits [V]; feeding the next token (``self.ids[b]``) and
         ``state.active[b]`` are the caller's. Paged cache: slot ``b`` is freed and ``max(len(ids),
         reserve)`` rows are reserved for it (``reserve``: the prompt plus the tokens the coming replays
-        will add); ``CacheFull`` leaves the slot as it was."""
+        will add); ``CacheFull`` leaves the slot as it was. ``chunk``: as :meth:`prefill`."""
         if not self.ragged:
             raise ValueError("GraphDecoder: prefill_row needs ragged=True")
+        if chunk is not None:
+            check_chunk(chunk)
+            _need_extend(self.model)
         if not 0 <= b < self.batch:
             raise IndexError(f"slot {b} of {self.batch}")
         ids = ids.reshape(1, -1)
@@ -265,17 +366,34 @@ class GraphDecoder:
                                 f"{self.cache.pages_free} are free and it holds {self.cache.held(b)}")
             self.cache.free(b)
             self.cache.reserve(b, rows)
-        lg = self.model.step(ids, self.cache.rows(b, b + 1), 0)
+        if chunk is not None:
+            lg = chunked_prefill(self.model, self.cache.rows(b, b + 1), ids,
+                                 torch.full((1,), T, dtype=torch.long, device=ids.device), chunk)
+        else:
+            lg = self.model.step(ids, self.cache.rows(b, b + 1), 0)
         self.state.set_row(b, T)
         return lg[0]
 
     @torch.no_grad()
+    def extend_row(self, b: int, ids: torch.Tensor, reserve: Optional[int] = None) -> torch.Tensor:
+        """Append ``ids`` (1-D) behind slot ``b``'s current position between replays (a new turn of a live
+        sequence) without re-running its history; the other slots keep their rows and positions
+        (``ragged=True``). Returns the last appended token's logits [V]; feeding the next token
+        (``self.ids[b]``) is the caller's. See :func:`extend_row`."""
+        if not self.ragged:
+            raise ValueError("GraphDecoder: extend_row needs ragged=True (the uniform state holds one position)")
+        return extend_row(self.model, self.cache, self.state, b, ids, reserve)
+
+    @torch.no_grad()
     def generate(self, ids: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k=None,
-                 top_p=None, generator=None, stats=None, prompt_lens=None, pad_token_id: int = 0) -> torch.Tensor:
+                 top_p=None, generator=None, stats=None, prompt_lens=None, pad_token_id: int = 0,
+                 prefill_chunk: Optional[int] = None) -> torch.Tensor:
         """``prompt_lens`` (``ragged=True``): right-padded prompts of different lengths; returns
         [B, T0 + n] with row b = its prompt, its n new tokens from column ``prompt_lens[b]``, then
-        ``pad_token_id``."""
+        ``pad_token_id``. ``prefill_chunk``: :meth:`prefill`'s ``chunk`` (needs ``prompt_lens``)."""
         import time
+        if prefill_chunk is not None and prompt_lens is None:
+            raise ValueError("GraphDecoder.generate: prefill_chunk needs prompt_lens (a ragged batch)")
         if self.sampler is not None and (temperature != 1.0 or top_k is not None or top_p is not None
                                          or generator is not None):
             raise ValueError("GraphDecoder: the captured sampler fixes temperature / top_k / top_p and draws from "
@@ -291,8 +409,8 @@ class GraphDecoder:
         # paged cache: each row's len + n rows are reserved before the replay loop (a pool too small raises
         # CacheFull here, before the cache or the positions change)
         held = [ids.shape[1]] * self.batch if lens is None else lens.tolist()
-        lg = self.prefill(ids, lens, reserve=[min(h + n, self.max_len) for h in held]) if self.paged else \
-            self.prefill(ids, lens)
+        lg = self.prefill(ids, lens, reserve=[min(h + n, self.max_len) for h in held] if self.paged else None,
+                          chunk=prefill_chunk)
         if stats is not None:
             torch.cuda.synchronize()
         t1 = time.perf_counter()

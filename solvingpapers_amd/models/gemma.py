@@ -26,7 +26,7 @@ import torch
 import torch.nn as tnn
 
 from .. import nn as snn
-from ..infer.graph import DecodeState
+from ..infer.graph import DecodeState, ExtendState
 from ..ops import attention_packed, embedding, glu, linear, linear_cross_entropy, rms_norm, rope_packed_
 from ..ops.linear import swiglu_mlp
 from ..ops.attention import flash_attention, kv_cache_attend, kv_cache_write, rope_kv_cache_write_
@@ -559,6 +559,20 @@ class Gemma(tnn.Module):
         if self.tp != 1:
             raise NotImplementedError("graph decode runs on one TP rank; use step() under tensor parallelism")
         n = self.hidden(ids, cache, state)
+        return linear(n, self.embed).float()[:, -1]
+
+    def extend(self, ids, cache, starts, last=None):
+        """Append ``ids`` [B, T] (right-padded) behind what ``cache`` holds: sequence b's tokens take
+        cache rows [starts[b], starts[b] + T) and attend over its rows before them. Returns the logits
+        [B, V] of position ``last[b]`` (default T - 1), gathered before the head. The pads write rows
+        beyond a sequence's real length, overwritten as it grows (the ragged prefill's contract).
+        Single TP rank, as ``step_graph``."""
+        from ..ops.layout import gather_rows
+        if self.tp != 1:
+            raise NotImplementedError("extend runs on one TP rank; use step() under tensor parallelism")
+        state = ExtendState(starts, ids.shape[1], cache.max_len, ids.device)
+        n = self.hidden(ids, cache, state)
+        n = n[:, -1:] if last is None else gather_rows(n, last)
         return linear(n, self.embed).float()[:, -1]
 
     @torch.no_grad()

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from ..infer.cache import new_kv_cache
-from ..infer.graph import DecodeState
+from ..infer.graph import DecodeState, ExtendState
 from ..infer.sampling import sample  # noqa: F401  (re-exported: reference-style sampling)
 from ..ops import attention_packed, embedding, linear, linear_cross_entropy, rms_norm, rope_packed_
 from ..ops.linear import swiglu_mlp
@@ -271,6 +271,15 @@ class Llama3(nn.Module):
         length from ``state.kv_len``."""
         n = self.hidden(ids, cache, state)
         return self.logits(n).float()[:, -1]
+
+    def extend(self, ids, cache, starts, last=None):
+        """Append ``ids`` [B, T] (right-padded) behind what ``cache`` holds: sequence b's tokens take
+        cache rows [starts[b], starts[b] + T) and attend over its rows before them. Returns the logits
+        [B, V] of position ``last[b]`` (default T - 1), gathered before the head. The pads write rows
+        beyond a sequence's real length, overwritten as it grows (the ragged prefill's contract)."""
+        state = ExtendState(starts, ids.shape[1], cache.max_len, ids.device)
+        n = self.hidden(ids, cache, state)
+        return self.logits(n[:, -1:] if last is None else gather_rows(n, last)).float()[:, -1]
 
     @torch.no_grad()
     def generate(self, ids, max_new_tokens, temperature=1.0, top_k=None, greedy=False, generator=None,

@@ -425,10 +425,29 @@ def _decode_ok(q, k, v):
                and t.data_ptr() % 8 == 0 for t in (q, k, v))
 
 
+def _extend_ok(q, kv, Tk, causal):
+    """The extend kernel (csrc/kernels/attention_extend.hip) serves this call: what the decode kernel
+    asks for, without its 16-row limit -- causal, bf16 on the GPU, hd 64 / 128 / 256, 16-byte rows."""
+    if not (causal and q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4 and q.shape[-1] in FLASH_HD):
+        return False
+    B, Tq, H, hd = q.shape
+    Hkv = kv[0].shape[2]
+    if H % Hkv or Tq * (H // Hkv) <= DECODE_MAX_ROWS or Tq > Tk:
+        return False
+    return all(t.dtype == torch.bfloat16 and t.dim() == 4 and t.stride(3) == 1 and t.stride(0) % 8 == 0
+               and t.stride(1) % 8 == 0 and t.stride(2) % 8 == 0 and t.data_ptr() % 16 == 0 for t in (q, *kv))
+
+
+# a device kv_len on the GPU with no kernel to read it (bf16 pair or pages)
+_KV_LEN_GPU = ("{}: kv_len on the GPU needs bf16 tensors at head dim 64 / 128 / 256 and Tq <= Tk, for the decode kernel "
+               "Tq * H / Hkv <= 16, past that (the extend kernel) causal attention and 16-byte-aligned rows")
+
+
 def decode_attention(q, k, v=None, causal=True, scale=None, nsplit=0, kv_len=None, per_row=False):
     """Few new query rows against a KV cache: q [B,Tq,H,hd], k/v [B,Tk,Hkv,hd] (cache views,
     the last Tq cache rows are the query tokens). Split-K HIP kernel (csrc/kernels/decode.hip)
-    when Tq * H / Hkv <= 16, else the flash kernel. Inference only (no autograd).
+    when Tq * H / Hkv <= 16; past that the extend kernel (csrc/kernels/attention_extend.hip) with a
+    device ``kv_len``, else the flash kernel. Inference only (no autograd).
 
     ``kv_len`` (device int32 [1]): k/v are whole cache buffers and only the first *kv_len
     rows are valid -- the form a captured hipGraph decode step replays at every position.
@@ -446,8 +465,10 @@ def decode_attention(q, k, v=None, causal=True, scale=None, nsplit=0, kv_len=Non
     if _decode_ok(q, k, v):
         return _ext.ops().attn_decode(q, k, v, scale, causal, int(nsplit), kv_len, per_row)[0]
     if kv_len is not None:
+        if _extend_ok(q, (k, v), k.shape[1], causal):
+            return _ext.ops().attn_extend(q, k, v, scale, kv_len, per_row)[0]
         if q.is_cuda:
-            raise ValueError("decode_attention: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
+            raise ValueError(_KV_LEN_GPU.format("decode_attention"))
         if per_row:
             return reference.attention_per_row(q, k, v, kv_len, causal, scale)[0]
         n = min(int(kv_len.reshape(-1)[0]), k.shape[1])
@@ -628,7 +649,8 @@ def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=
     CPU, through the oracle). ``per_row``: ``kv_len`` is int32 [B], one length per sequence.
 
     A :class:`PagedKV` layer (``n`` None: its ``max_len`` rows): ``fresh`` as above; else
-    attn_decode_paged through the block table when the decode kernel applies; else rows [0, n) are
+    attn_decode_paged through the block table when the decode kernel applies; attn_extend_paged when
+    only its 16-row limit is in the way and a device ``kv_len`` is given; else rows [0, n) are
     gathered into a contiguous [B, n, Hkv, hd] pair that takes :func:`decode_attention`'s route."""
     if isinstance(cache, PagedKV):
         if per_row and kv_len is None:
@@ -642,8 +664,12 @@ def kv_cache_attend(q, cache, n=None, causal=True, scale=None, nsplit=0, kv_len=
             sc = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
             return _ext.ops().attn_decode_paged(q, cache.k, cache.v, cache.block_table, sc, causal, int(nsplit),
                                                 int(rows), kv_len, per_row)[0]
+        if kv_len is not None and _extend_ok(q, (cache.k, cache.v), rows, causal):
+            sc = float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+            return _ext.ops().attn_extend_paged(q, cache.k, cache.v, cache.block_table, sc, int(rows), kv_len,
+                                                per_row)[0]
         if kv_len is not None and q.is_cuda:
-            raise ValueError("kv_cache_attend: kv_len needs the decode kernel (Tq * H / Hkv <= 16, bf16 on the GPU)")
+            raise ValueError(_KV_LEN_GPU.format("kv_cache_attend"))
         k, v = cache.gathered(rows)
         return decode_attention(q, k, v, causal=causal, scale=scale, nsplit=nsplit, kv_len=kv_len, per_row=per_row)
     if not isinstance(cache, KV8):

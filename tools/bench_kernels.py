@@ -10,7 +10,11 @@ just the token-sampler rows: the fused kernel (sample_logits) beside the eager i
 attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes, then
 the per_row (ragged batch) form of both kernels at batch 16: equal lengths and lengths spread 1:4, then
 attn_decode_paged (paged KV cache, 16- and 64-row pages in shuffled order) against attn_decode on the same
-rows (``--only decode_attn_paged``: those rows alone).
+rows (``--only decode_attn_paged``: those rows alone). ``--only attn_extend`` runs just the extend-attention rows:
+attn_extend (device per-sequence lengths) against attn_fwd (host length) at the same Tq / Tk, attn_extend_paged
+(16- and 64-row pages in shuffled order) against gather + attn_fwd (``attn_extend_kernels``: those rows alone), and
+(``attn_extend_e2e``: that alone) a chunked against a one-pass GraphDecoder.prefill of 16 ragged LLaMA3-8B prompts
+with its peak memory.
 """
 import argparse
 import json
@@ -314,6 +318,121 @@ def decode_attn_paged_rows(iters, rounds=3):
         del rings, arms
 
 
+# (H, Hkv, hd, B, Tq, Tk): a 512-token chunk against 2K / 8K / 32K cache rows at LLaMA3-8B heads, the same at
+# Gemma's MQA hd 256, and a 64-token turn against 8K rows
+ATTN_EXTEND_SHAPES = [(32, 8, 128, B, 512, Tk) for Tk in (2048, 8192, 32768) for B in (1, 4)] + \
+    [(16, 1, 256, 1, 512, 8192), (16, 1, 256, 4, 512, 8192), (32, 8, 128, 1, 64, 8192), (32, 8, 128, 4, 64, 8192)]
+
+
+def attn_extend_rows(iters, rounds=3):
+    """Arm 1: attn_extend over the contiguous cache (device kv_len [B], every length Tk) against attn_fwd with the
+    host length at the same Tq / Tk -- the same MFMA loop, so ``time_vs_fwd`` near 1 is the expectation. Arm 2:
+    attn_extend_paged through shuffled 16- and 64-row pages against PagedKV.gathered + attn_fwd, what a paged
+    multi-token step at a host length runs (``time_vs_gather_fwd``, the gather included). Each arm is one HIP-graph
+    replay, the six arms alternated A B C D E F F E D C B A per round, medians reported with min / max. TFLOP/s counts the causal
+    work 4 * hd * H * B * Tq * (Tk - Tq / 2)."""
+    from solvingpapers_amd.ops.attention import PagedKV
+    ops = _ext.ops()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for H, Hkv, hd, B, Tq, Tk in ATTN_EXTEND_SHAPES:
+        q = torch.randn(B, Tq, H, hd, device=DEV, dtype=BF, generator=g)
+        k, v = (torch.randn(B, Tk, Hkv, hd, device=DEV, dtype=BF, generator=g) for _ in range(2))
+        sc = hd ** -0.5
+        kv_len = torch.full((B,), Tk, device=DEV, dtype=torch.int32)
+        layers = {}
+        for page in (16, 64):
+            NP = Tk // page
+            perm = torch.randperm(B * NP, generator=torch.Generator().manual_seed(page)) + 1
+            bt = perm.view(B, NP).to(DEV, torch.int32)
+            kp, vp = (torch.zeros(B * NP + 1, page, Hkv, hd, device=DEV, dtype=BF) for _ in range(2))
+            kp[bt.long().flatten()] = k.view(B * NP, page, Hkv, hd)
+            vp[bt.long().flatten()] = v.view(B * NP, page, Hkv, hd)
+            layers[page] = PagedKV(kp, vp, bt, page, Tk)
+        o0 = ops.attn_extend(q, k, v, sc, kv_len, True)[0]
+        f0 = ops.attn_fwd(q, k, v, sc, True, 0.0, 0, None)[0]
+        err = ((o0.float() - f0.float()).norm() / f0.float().norm()).item()
+        for page, l in layers.items():     # the same bits through the table, before anything is timed
+            assert torch.equal(ops.attn_extend_paged(q, l.k, l.v, l.block_table, sc, Tk, kv_len, True)[0], o0)
+
+        def gather_fwd(l):
+            kg, vg = l.gathered(Tk)
+            return ops.attn_fwd(q, kg, vg, sc, True, 0.0, 0, None)
+
+        arms = {"fwd": _graphed(lambda: ops.attn_fwd(q, k, v, sc, True, 0.0, 0, None)),
+                "extend": _graphed(lambda: ops.attn_extend(q, k, v, sc, kv_len, True))}
+        for page, l in layers.items():
+            arms[f"paged{page}"] = _graphed(lambda l=l: ops.attn_extend_paged(q, l.k, l.v, l.block_table, sc, Tk,
+                                                                              kv_len, True))
+            arms[f"gather_fwd{page}"] = _graphed(lambda l=l: gather_fwd(l))
+        order = list(arms)
+        ms = {a: [] for a in arms}
+        for _ in range(rounds):
+            for arm in order + order[::-1]:
+                ms[arm].append(timed(arms[arm], iters))
+        med = {a: sorted(t)[len(t) // 2] for a, t in ms.items()}
+        flop = 4.0 * hd * H * B * Tq * (Tk - Tq / 2)
+        base = {"extend": ("time_vs_fwd", "fwd"), "paged16": ("time_vs_gather_fwd", "gather_fwd16"),
+                "paged64": ("time_vs_gather_fwd", "gather_fwd64")}
+        names = {"fwd": "attn_fwd", "extend": "attn_extend", "paged16": "attn_extend_paged_page16",
+                 "paged64": "attn_extend_paged_page64", "gather_fwd16": "gather+attn_fwd_page16",
+                 "gather_fwd64": "gather+attn_fwd_page64"}
+        for a in arms:
+            row = {"kernel": f"{names[a]}_B{B}_Tq{Tq}_Tk{Tk}_H{H}kv{Hkv}_hd{hd}", "ms": round(med[a], 5),
+                   "TFLOP_per_s": round(flop / med[a] / 1e9, 1), "min_ms": round(min(ms[a]), 5),
+                   "max_ms": round(max(ms[a]), 5)}
+            if a in base:
+                row[base[a][0]] = round(med[a] / med[base[a][1]], 3)
+            if a == "paged16" or a == "paged64":
+                row["time_vs_extend"] = round(med[a] / med["extend"], 3)
+            if a == "extend":
+                row["rel_l2_vs_fwd"] = float(f"{err:.3e}")
+            print(json.dumps(row), flush=True)
+        del arms, layers
+
+
+def attn_extend_e2e_rows(rounds=2, chunk=512, layers=None):
+    """Arm 3: GraphDecoder.prefill of 16 ragged LLaMA3-8B prompts of 2K..8K tokens into a paged cache (64-row
+    pages), chunk=512 against chunk=None: one decoder, the two alternated A B B A per round, each timed between
+    device synchronisations with its own torch.cuda.max_memory_allocated (the peak is reset before each)."""
+    import time
+    from solvingpapers_amd.infer import GraphDecoder
+    from solvingpapers_amd.models import llama3
+    kw = {} if layers is None else {"n_layers": layers}
+    m = llama3.Llama3(llama3.config("llama3_8b", **kw), device=DEV, dtype=BF, seed=1).eval()
+    lens = [2048 + (6080 * i) // 15 for i in range(16)]     # 2048 .. 8128: the longest plus 64 rows is the 8K context
+    ids = torch.randint(0, m.c.vocab_size, (16, max(lens)), device=DEV)
+    dec = GraphDecoder(m, 16, max(lens) + 64, ragged=True, page_size=64)
+    res = {"chunked": [], "one_pass": []}
+    logits = {}
+
+    def run(arm):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        logits[arm] = dec.prefill(ids, lens, chunk=chunk if arm == "chunked" else None)
+        torch.cuda.synchronize()
+        res[arm].append((time.perf_counter() - t0, torch.cuda.max_memory_allocated()))
+
+    run("one_pass"), run("chunked")            # warm-up of both paths (kernels, allocator, GEMM selection)
+    res = {"chunked": [], "one_pass": []}
+    for _ in range(rounds):
+        for arm in ("chunked", "one_pass", "one_pass", "chunked"):
+            run(arm)
+    base = torch.cuda.memory_allocated()       # weights, cache, graph pools: held by both arms
+    err = ((logits["chunked"] - logits["one_pass"]).norm() / logits["one_pass"].norm()).item()
+    med = {a: sorted(t for t, _ in r)[len(r) // 2] for a, r in res.items()}
+    for a, r in res.items():
+        peak = max(p for _, p in r)
+        print(json.dumps({"kernel": f"llama3_8b_prefill_{a}_16x2K..8K_page64" + (f"_chunk{chunk}" if a == "chunked" else ""),
+                          "s": round(med[a], 4), "min_s": round(min(t for t, _ in r), 4),
+                          "max_s": round(max(t for t, _ in r), 4), "prompt_tokens": sum(lens),
+                          "tok_per_s": round(sum(lens) / med[a], 1), "peak_mem_GB": round(peak / 1e9, 3),
+                          "peak_above_resident_GB": round((peak - base) / 1e9, 3),
+                          **({"time_vs_one_pass": round(med[a] / med["one_pass"], 3),
+                              "logits_rel_l2_vs_one_pass": float(f"{err:.3e}")} if a == "chunked" else {})}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -330,7 +449,12 @@ def main():
         decode_attn_per_row_rows(a.iters)
     if not only or only & {"decode_attn", "decode_attn_paged"}:
         decode_attn_paged_rows(a.iters)
-    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn", "decode_attn_paged"}
+    if not only or only & {"attn_extend", "attn_extend_kernels"}:
+        attn_extend_rows(a.iters)
+    if only & {"attn_extend", "attn_extend_e2e"}:      # builds a LLaMA3-8B: never part of a plain run (no --only)
+        attn_extend_e2e_rows()
+    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn", "decode_attn_paged",
+                                                       "attn_extend", "attn_extend_kernels", "attn_extend_e2e"}
                                else cases()).items():
         if only and name not in only:
             continue
