@@ -4,7 +4,8 @@
 Default: LLaMA3-8B shape, bf16, random-init weights, synthetic prompt. Reports prefill
 tok/s and decode tok/s (all sequences); one JSON line. ``--weights fp8`` decodes from the
 block-scaled e4m3 images of infer.quantize_decode_weights, ``--weights mxfp4`` from its OCP MXFP4 images
-(prefill stays on bf16);
+(prefill stays on bf16); ``--weight-rows N`` (4..16, with ``--weights fp8|mxfp4``) builds them with ``max_rows=N``, so a
+batch of up to N sequences decodes from the images too (csrc/kernels/skinny_gemm.hip), and adds ``weight_rows`` to the result line;
 ``--kv-cache fp8`` keeps the KV cache as e4m3 rows with per-row E8M0 scales (infer/cache.py) and
 decodes with attn_decode_q8 -- the cache's size is reported as ``kv_cache_bytes`` either way. The
 ``--sampler`` picks how the next token is drawn: ``greedy`` (argmax, captured with
@@ -66,6 +67,9 @@ def main(argv=None):
     ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
                     help="fp8: decode products read e4m3 weight images (128x128 E8M0 block scales); "
                          "mxfp4: e2m1 images (1x32 E8M0 block scales)")
+    ap.add_argument("--weight-rows", type=int, default=None,
+                    help="with --weights fp8|mxfp4: quantize_decode_weights(max_rows=N), N in [4, 16]: products of up "
+                         "to N token rows read the images (default: 4, the GEMV routes alone)")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: e4m3 KV cache with one E8M0 scale per (batch, kv head, token) row")
     ap.add_argument("--sampler", choices=["greedy", "eager", "fused"], default="greedy",
@@ -90,6 +94,8 @@ def main(argv=None):
         ap.error("--prefill-chunk needs --prompt-lens (a ragged batch)")
     if a.pages is not None and a.page_size is None:
         ap.error("--pages needs --page-size")
+    if a.weight_rows is not None and a.weights == "bf16":
+        ap.error("--weight-rows needs --weights fp8 or mxfp4")
     pkw = {} if a.page_size is None else {"page_size": a.page_size, "num_pages": a.pages}
     lens = None
     if a.prompt_lens is not None:
@@ -101,9 +107,12 @@ def main(argv=None):
         extra.update(page_size=a.page_size)
     if a.weights != "bf16":
         from solvingpapers_amd.infer import quantize_decode_weights
-        rep = quantize_decode_weights(m) if a.weights == "fp8" else quantize_decode_weights(m, fmt=a.weights)
+        qkw = {} if a.weight_rows is None else {"max_rows": a.weight_rows}   # {}: the call as before the option existed
+        rep = quantize_decode_weights(m, **qkw) if a.weights == "fp8" else quantize_decode_weights(m, fmt=a.weights, **qkw)
         extra = {"weights": rep["format"], "image_bytes": rep["image_bytes"],
                  "quantized_params": len(rep["quantized"]), "bf16_params": len(rep["bf16"])}
+        if a.weight_rows is not None:
+            extra["weight_rows"] = rep["max_rows"]
     kvc = None if a.kv_cache == "bf16" else a.kv_cache     # None: every call as before the option existed
     ckw = {} if kvc is None else {"kv_cache": kvc}
     ids = torch.randint(0, m.c.vocab_size, (a.batch, a.prompt), device="cuda")

@@ -284,21 +284,22 @@ def mlp(x, w1, b1, w2, b2, kind="gelu", alpha=None):
     return linear(linear_act(x, w1, b1, kind, alpha), w2, b2)
 
 
-def _gemv_ok(x, w, b) -> bool:
+def _gemv_ok(x, w, b, max_rows=GEMV_MAX_ROWS) -> bool:
     """Decode-shaped inference product (<= GEMV_MAX_ROWS token rows, no autograd): routed to
-    the weight-streaming GEMV kernel (csrc/kernels/gemv.hip) instead of a library GEMM."""
+    the weight-streaming GEMV kernel (csrc/kernels/gemv.hip) instead of a library GEMM. ``max_rows``: the
+    row limit of a weight whose decode image was built with ``max_rows`` above 4 (:func:`_decode_linear`)."""
     if not (GEMV and b is None and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         return False
     K = x.shape[-1]
     rows = x.numel() // K if K else 0
-    return (1 <= rows <= GEMV_MAX_ROWS and K % 8 == 0 and w.dim() == 2 and w.stride(1) == 1
+    return (1 <= rows <= max_rows and K % 8 == 0 and w.dim() == 2 and w.stride(1) == 1
             and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0 and x.stride(-1) == 1
             and x.data_ptr() % 16 == 0)
 
 
-def _w8_cpu_ok(x, w, b) -> bool:
+def _w8_cpu_ok(x, w, b, max_rows=GEMV_MAX_ROWS) -> bool:
     """:func:`_gemv_ok`'s conditions on the CPU: a decode-shaped inference product there reads a
     weight's decode image (fp8 or MXFP4) through the oracle, so a quantised model decodes the same on both."""
     if x.is_cuda or b is not None or w.dim() != 2 or not x.is_floating_point():
@@ -306,7 +307,7 @@ def _w8_cpu_ok(x, w, b) -> bool:
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         return False
     K = x.shape[-1]
-    return 1 <= (x.numel() // K if K else 0) <= GEMV_MAX_ROWS
+    return 1 <= (x.numel() // K if K else 0) <= max_rows
 
 
 class _LinearFP8Fn(torch.autograd.Function):
@@ -397,19 +398,32 @@ def _decode_linear(x, w, b):
     """x w^T of a decode-shaped inference product on the weight-streaming GEMV, or None where the
     product is not one. The weight's fp8 or MXFP4 decode image where it carries one (``gemv_w8`` /
     ``gemv_w4``; on the CPU, :func:`_w8_cpu_ok`, the dequantised oracle product), else the bf16 master
-    (``gemv``)."""
+    (``gemv``).
+
+    Products of 1..GEMV_MAX_ROWS rows take those routes whatever else is set. A weight whose image was built
+    with ``quantize_decode_weights(..., max_rows=R)``, R up to 16, also serves products of 5..R rows from the
+    image: ``skinny_gemm_w8`` / ``skinny_gemm_w4`` on the GPU (csrc/kernels/skinny_gemm.hip, one MFMA row tile),
+    the same oracle product on the CPU, under the same conditions (no autograd, no bias, aligned rows) and the same
+    stale-image check. That holds for ANY such inference product, not only a one-token decode step: a 10-token
+    ``prefill_row`` and an 8-row product read the image too. At the default (``max_rows=4``), without an image,
+    and above R rows this returns None as it always did and the product runs on the bf16 master."""
     # quantize_decode_weights keeps one image per parameter; were both attached, fp8 (the default) wins
     if getattr(w, "_spa_w8", None) is not None:
-        name, image = "gemv_w8", "w8_image"
+        name, image, skinny = "gemv_w8", "w8_image", "skinny_gemm_w8"
     elif getattr(w, "_spa_w4", None) is not None:
-        name, image = "gemv_w4", "w4_image"
+        name, image, skinny = "gemv_w4", "w4_image", "skinny_gemm_w4"
     else:
-        name, image = "gemv", None
-    if _gemv_ok(x, w, b):
-        op = getattr(_ext.ops(), name)
-    elif image is not None and _w8_cpu_ok(x, w, b):
+        name, image, skinny = "gemv", None, None
+    max_rows = GEMV_MAX_ROWS
+    if image is not None:
+        max_rows = max(GEMV_MAX_ROWS, getattr(w, "_spa_wrows", GEMV_MAX_ROWS))
+    K = x.shape[-1]
+    wide = (x.numel() // K if K else 0) > GEMV_MAX_ROWS      # only ever true with an image and max_rows above 4
+    if _gemv_ok(x, w, b, max_rows):
+        op = getattr(_ext.ops(), skinny if wide else name)
+    elif image is not None and _w8_cpu_ok(x, w, b, max_rows):
         from . import reference
-        op = getattr(reference, name)
+        op = getattr(reference, name)                        # the oracle product has no row limit
     else:
         return None
     from . import moe
@@ -424,7 +438,8 @@ def linear(x, w, b=None, fp8=False):
     """y = x w^T (+ b). ``fp8``: e4m3 forward / dX on hipBLASLt with row-wise scales (dims
     multiples of 16; else bf16). A decode-shaped inference product goes to the GEMV kernels
     (csrc/kernels/gemv.hip), ``fp8`` or not, and reads the weight's fp8 or MXFP4 decode image
-    (infer.quantize_decode_weights) where it carries one (:func:`_decode_linear`)."""
+    (infer.quantize_decode_weights) where it carries one (:func:`_decode_linear`); with images built with
+    ``max_rows`` above 4, so does an inference product of up to that many rows (csrc/kernels/skinny_gemm.hip)."""
     y = _decode_linear(x, w, b)
     if y is not None:
         return y
@@ -507,7 +522,9 @@ def linear_rows(x, ws):
     per pass when the weights sit back to back in a FlatParams buffer (Gemma's q and MQA K/V
     projections), else the concatenation of separate products."""
     jv = _joint_views(ws)
-    if jv is not None and not _gemv_ok(x, jv[0], None):
+    # weights whose decode images serve this many rows (max_rows above 4) keep their separate image products
+    rows = max((getattr(w, "_spa_wrows", GEMV_MAX_ROWS) for w in ws), default=GEMV_MAX_ROWS)
+    if jv is not None and not _gemv_ok(x, jv[0], None, max(rows, GEMV_MAX_ROWS)):
         return _LinearRowsFn.apply(x, jv[0], jv[1], *ws)
     return torch.cat([linear(x, w) for w in ws], dim=-1)
 

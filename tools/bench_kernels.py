@@ -4,7 +4,9 @@ as achieved HBM bandwidth (ideal bytes / time). Run under ``rocprofv3 --pmc`` fo
 usage: python tools/bench_kernels.py [--iters N] [--only name,name]
 
 ``--only gemv`` runs just the decode GEMV rows: the fp8 and MXFP4 weight-only kernels (gemv_w8, gemv_w4)
-against the bf16 kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only sample`` runs
+against the bf16 kernel (gemv) at the four LLaMA3-8B projection shapes, M = 1 and 4. ``--only skinny`` runs just
+the 5..16-row weight-only rows: skinny_gemm_w8 and skinny_gemm_w4 on the images against torch.mm on the bf16 master
+(what such a product runs on today) at those shapes and the LM head, M = 8 and 16. ``--only sample`` runs
 just the token-sampler rows: the fused kernel (sample_logits) beside the eager infer.sample() on the same logits.
 ``--only decode_attn`` runs just the decode-attention rows: attn_decode_q8 over an fp8 KV cache against
 attn_decode over the bf16 cache at LLaMA3-8B (H 32/8, hd 128) and Gemma-7B (H 16/1, hd 256) shapes, then
@@ -152,6 +154,48 @@ def gemv_rows(iters, rounds=3):
                                   "weight_GB_per_s": round(nbytes / med[key] / 1e6, 1),
                                   "min_ms": round(min(ms[key]), 5), "max_ms": round(max(ms[key]), 5), **ratios}),
                       flush=True)
+        del wb, wf, w4s
+
+
+SKINNY_SHAPES = GEMV_SHAPES + [(128256, 4096)]                             # .. and the LM head
+
+
+def skinny_rows(iters, rounds=3):
+    """skinny_gemm_w8 and skinny_gemm_w4 next to torch.mm on the bf16 master (the route of a 5..16-row product
+    without ``max_rows``), same process, arms alternated A B C C B A per round, as ``gemv_rows``: every call reads
+    another copy of the weight out of a ring larger than the 256 MB last-level cache (>= 0.5 GB of the smallest
+    format), one pass over the ring is one HIP-graph replay. Reported: time, GB/s of WEIGHT bytes (scales
+    included) and the time ratio to the bf16 product (< 1: the image is faster)."""
+    from solvingpapers_amd.ops.moe import quant_weight_fp8_blk_uncached, quant_weight_mxfp4
+    ops = _ext.ops()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for N, K in SKINNY_SHAPES:
+        ring = max(32, -(-(1 << 30) // (N * K))) if N * K < (1 << 28) else 3   # the LM head: 3 x 0.28 GB of mxfp4
+        w = torch.randn(N, K, device=DEV, dtype=BF, generator=g)
+        wq, _, s, _ = quant_weight_fp8_blk_uncached(w[None])
+        w4, s4 = quant_weight_mxfp4(w[None])
+        wb = [w.clone() for _ in range(ring)]
+        wf = [(wq[0].clone(), s[0].clone()) for _ in range(ring)]
+        w4s = [(w4[0].clone(), s4[0].clone()) for _ in range(ring)]
+        del w, wq, w4
+        for M in (8, 16):
+            x = torch.randn(M, K, device=DEV, dtype=BF, generator=g)
+            arms = {"bf16": _graphed(lambda: [torch.mm(x, wi.t()) for wi in wb]),
+                    "fp8": _graphed(lambda: [ops.skinny_gemm_w8(x, q, si) for q, si in wf]),
+                    "mxfp4": _graphed(lambda: [ops.skinny_gemm_w4(x, q, si) for q, si in w4s])}
+            ms = {a: [] for a in arms}
+            for _ in range(rounds):
+                for arm in ("bf16", "fp8", "mxfp4", "mxfp4", "fp8", "bf16"):
+                    ms[arm].append(timed(arms[arm], iters) / ring)
+            med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+            for arm, key, nbytes in (("mm_bf16", "bf16", N * K * 2), ("skinny_gemm_w8", "fp8", N * K + N * K // 16384),
+                                     ("skinny_gemm_w4", "mxfp4", N * K // 2 + N * K // 32)):
+                ratios = {} if key == "bf16" else {"time_vs_bf16": round(med[key] / med["bf16"], 3)}
+                print(json.dumps({"kernel": f"{arm}_M{M}_{N}x{K}", "ms": round(med[key], 5), "GB": round(nbytes / 1e9, 4),
+                                  "weight_GB_per_s": round(nbytes / med[key] / 1e6, 1),
+                                  "min_ms": round(min(ms[key]), 5), "max_ms": round(max(ms[key]), 5), **ratios}),
+                      flush=True)
+            del arms
         del wb, wf, w4s
 
 
@@ -442,6 +486,8 @@ def main():
     only = set(filter(None, a.only.split(",")))
     if not only or "gemv" in only:
         gemv_rows(a.iters)
+    if not only or "skinny" in only:
+        skinny_rows(a.iters)
     if not only or "sample" in only:
         sample_rows(a.iters)
     if not only or "decode_attn" in only:
@@ -453,7 +499,7 @@ def main():
         attn_extend_rows(a.iters)
     if only & {"attn_extend", "attn_extend_e2e"}:      # builds a LLaMA3-8B: never part of a plain run (no --only)
         attn_extend_e2e_rows()
-    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "sample", "decode_attn", "decode_attn_paged",
+    for name, (fn, nbytes) in ({} if only and only <= {"gemv", "skinny", "sample", "decode_attn", "decode_attn_paged",
                                                        "attn_extend", "attn_extend_kernels", "attn_extend_e2e"}
                                else cases()).items():
         if only and name not in only:
